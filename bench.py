@@ -9,18 +9,28 @@ epilogue) and the per-target batch totals -- one launch of the chroma-run
 kernel at this size (the fused step) -- then the RCCL all-reduce of the totals
 across GPUs when N > 1.
 
-Before the warmup (untimed for `value`, reported in their own fields): the
-first call of a fresh handle, a batch with a new range set (cold_batch), and
-the same step on scene frames (`scene`).
+A plain run sets up, warms up, times the steps and prints the line.  Its
+setup ends with 60 untimed launches of the step (`--ramp-launches`, 30 ms):
+the first launches after an idle device run up to 40 % slower until the clocks
+are up, and `value` is the rate of a running workload.  With
+`--dump-outputs DIR` it then writes what the last timed step returned (the
+per-frame sums and targets and the batch totals) as DIR/<name>.npy; the inputs
+are seeded, so two builds can be compared output for output.
+
+Everything else is behind `--full`.  Before the warmup (untimed for `value`,
+reported in their own fields): the first call of a fresh handle, a batch with
+a new range set (cold_batch), and the same step on scene frames (`scene`,
+SURVEY 8(d)(ii)).  After the timed steps: the totals check, the PMC traffic
+figure of the roofline, and the CPU baseline.
 
 With N GPUs (torch.distributed.run, one process per GPU) each rank owns its
 own 4096 frames (global frames rank*4096 ...): weak scaling; at N = 8 this is
 BASELINE configs[4] (32768 frames over 8 GPUs).
 
 Prints one JSON line (rank 0).  `roofline` is measured live with HIP events
-around the hot kernel on the stream it is launched on; `cpu_baseline` times
-the repo's CPU oracle (oracle/, test infrastructure) on a bounded sample of
-the same frames on this host's cores.
+around the hot kernel on the stream it is launched on; `cpu_baseline` (--full)
+times the repo's CPU oracle (oracle/, test infrastructure) on a bounded sample
+of the same frames on this host's cores.
 """
 import argparse
 import json
@@ -72,17 +82,28 @@ def parse():
                     help="CPU sample on every allowed thread when that exceeds the quota (oversubscribed)")
     ap.add_argument("--scene-launches", type=int, default=60,
                     help="launches timed on scene frames right before the warmup (0: none)")
+    ap.add_argument("--ramp-launches", type=int, default=60,
+                    help="plain run: untimed launches of the step right before the warmup, which bring the clocks "
+                         "up as the scene block of --full does (0: none)")
     ap.add_argument("--cpu-frames-1core", type=int, default=64, help="single-thread CPU sample")
     ap.add_argument("--cpu-frames-emul", type=int, default=32,
                     help="sample of the oracle's intrinsic-level emulation (secondary rate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the first call and "
+                         "cold-batch cost, scene frames, the totals check, the roofline's PMC traffic figure and "
+                         "the CPU baseline (a plain run: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy: sums "
+                         "[F,T,3] and totals [T,3] as float64 (exact: below 2^53), targets [F,T,4] as float32 "
+                         "(rank r > 0 of several writes <name>_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--event-every", type=int, default=0,
                     help="bracket every n-th timed step with HIP events for kernel_ms; 0 (default): one event "
                          "pair around the whole timed region when a step is one launch on the stream (the "
                          "fused step at N = 1), else every 4th step (an event record is a stream packet of a "
                          "few us: it delays the launch it brackets)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the cold-batch and scene measurements (PMC passes: only the bench's own launches)")
+                    help="with --full: skip the cold-batch and scene measurements")
     ap.add_argument("--hot", choices=["auto", "stripe", "chroma"], default="auto",
                     help="hot kernel (auto = the library's choice: chroma-run for this batch size)")
     ap.add_argument("--collective", choices=["comm", "torch"], default="comm",
@@ -99,6 +120,8 @@ def parse():
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_latest.json"),
                     help="rocprofv3 FETCH_SIZE summary used for roofline.traffic (when measured on these sources)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     for k, v in WORKLOADS[args.workload].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -229,6 +252,20 @@ def load_traffic(path, bytes_per_launch):
         return None, f"none: {rel} was measured on other sources ({pmc.get('source_digest')})"
     return pmc.get("hbm_read_bytes_per_launch"), (f"committed PMC pass, {rel} (FETCH_SIZE x 2, "
                                                   f"{pmc.get('measured', 'rocprofv3 --pmc')}; same sources)")
+
+
+def dump_outputs(out_dir, rank, sums, targets, totals):
+    """--dump-outputs: what the last timed step returned to its caller, one .npy
+    each (C3: 0.7 MB in all).  sums int64 [F,T,3] and totals int64 [T,3] (after
+    the all-reduce when N > 1) as float64: at most frames x pixels x width,
+    far below 2^53, so exact; targets int8 [F,T,4] as float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if rank == 0 else f"_rank{rank}"
+    for name, t, dt in (("sums", sums, np.float64), ("targets", targets, np.float32),
+                        ("totals", totals, np.float64)):
+        np.save(os.path.join(out_dir, f"{name}{tag}.npy"), t.cpu().numpy().astype(dt))
 
 
 def main():
@@ -364,10 +401,15 @@ def main():
         torch.cuda.synchronize()
         return c0.elapsed_time(c1), host_ms
 
-    # --- untimed for `value`, before the warmup ---------------------------
+    extras = args.full and not args.no_extras
+
+    # --- --full: untimed for `value`, before the warmup ---------------------
     # the first call of a fresh handle: table memory allocated, range tables
     # compiled on the host and uploaded, chroma-run tables built on the device
-    first_ms, first_host_ms = timed_call(ranges)
+    # (a plain run pays it in its first warmup step)
+    first_ms = first_host_ms = float("nan")
+    if args.full:
+        first_ms, first_host_ms = timed_call(ranges)
     # range sets the handle has not seen, on a warm handle (its table slots
     # already allocated): what a workload that changes ranges pays per change;
     # three new sets, each timed cold and then again (its steady cost), the
@@ -377,7 +419,7 @@ def main():
         return [(r[0] + j if k == 0 else r[0],) + tuple(r[1:]) for k, r in enumerate(ranges)]
     new_ms = new_host_ms = warm_ms = float("nan")
     cold_pairs = []
-    if not args.no_extras:
+    if extras:
         for j in range(1, 5):  # fill the handle's table slots (4) with other sets
             timed_call(shifted(j))
         for j in (5, 9, 13):  # (hue bounds far enough apart to pack differently)
@@ -387,14 +429,15 @@ def main():
         cold_pairs.sort(key=lambda p: p[0] - p[1])
         new_ms, warm_ms, new_host_ms = cold_pairs[len(cold_pairs) // 2]
         timed_call(ranges)  # back to the bench set (rebuilt)
-    full_step(frames, ranges)
+    if args.full:
+        full_step(frames, ranges)
     # scene frames: camera-like content, the same step.
     # Last before the warmup, back to back: the timed steps then start from
     # the clocks of a running workload, not from the power controller's
     # transient after the idle gaps above (profiles/r04/r04a_driver_cmd_launches.txt:
     # the same launch ran 478-700 us across those phases)
     scene = None
-    if args.scene_launches > 0 and not args.no_extras:
+    if args.scene_launches > 0 and extras:
         sframes = torch.empty_like(frames)
         trik_hsv.synth(sframes, W, H, ll, trik_hsv.LAYOUT_YUYV, 1, SEED, first_frame=first)
         full_step(sframes, ranges)
@@ -413,6 +456,13 @@ def main():
                  "data": "synthetic: device scene generator (gradients + 6 discs), seed 0x7A1C",
                  "note": "the same full step on scene frames, timed back to back right before the warmup "
                          "(not in `value`)"}
+
+    # a plain run has no scene block: the same number of launches of the step
+    # itself, back to back, takes its place in bringing the clocks up (30 ms),
+    # so that `value` is a running workload's whatever the warmup count
+    if not args.full:
+        for _ in range(args.ramp_launches):
+            full_step(frames, ranges)
 
     # --- the timed steps ----------------------------------------------------
     for _ in range(args.warmup):
@@ -450,20 +500,24 @@ def main():
     elapsed = time.perf_counter() - t0
     region_ms = region[0].elapsed_time(region[1]) / args.steps
     kern_ms = sum(a.elapsed_time(b) for a, b in evs) / len(evs) if evs else region_ms
-    # what the timed steps reduced: the totals after the last step against a
-    # fresh sum of this rank's per-frame sums, reduced the same way
     totals = last
-    fresh = batch_totals(sums)
-    if comm is not None:
-        comm.all_reduce_totals(fresh, stream=stream)
-        torch.cuda.synchronize()
-    elif backend == "nccl":
-        all_reduce_totals(fresh)
-    elif world > 1:
-        fresh = all_reduce_totals(fresh.cpu()).to(dev)
-    totals_ok = bool(torch.equal(fresh, totals))
-    if comm is not None:  # the other buffer holds the step before's reduction: the same frames
-        totals_ok = totals_ok and bool(torch.equal(totals_buf[0], totals_buf[1]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, sums, targets, totals)
+    # --full: what the timed steps reduced: the totals after the last step
+    # against a fresh sum of this rank's per-frame sums, reduced the same way
+    totals_ok = True
+    if args.full:
+        fresh = batch_totals(sums)
+        if comm is not None:
+            comm.all_reduce_totals(fresh, stream=stream)
+            torch.cuda.synchronize()
+        elif backend == "nccl":
+            all_reduce_totals(fresh)
+        elif world > 1:
+            fresh = all_reduce_totals(fresh.cpu()).to(dev)
+        totals_ok = bool(torch.equal(fresh, totals))
+        if comm is not None:  # the other buffer holds the step before's reduction: the same frames
+            totals_ok = totals_ok and bool(torch.equal(totals_buf[0], totals_buf[1]))
     ranks = dist.get_world_size() if world > 1 else 1
     kind = det.last_hot_kernel()
     kname = {trik_hsv.HOT_CHROMA: "chroma_kernel", trik_hsv.HOT_STRIPE: "stripe_kernel",
@@ -485,7 +539,8 @@ def main():
     value = px_total / elapsed / 1e6
     bytes_per_launch = F * fb  # algorithmic: 2 B/pixel read once
     achieved = bytes_per_launch / (kern_ms / 1e3) / 1e9
-    traffic, traffic_source = load_traffic(args.pmc, bytes_per_launch)
+    traffic, traffic_source = (load_traffic(args.pmc, bytes_per_launch) if args.full
+                               else (None, "none: not looked up (--full)"))
     out = {
         "metric": METRIC, "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup,
@@ -494,10 +549,6 @@ def main():
         "dtype": "u8", "ranks": ranks, "backend": (("nccl (RCCL)" if backend == "nccl" else backend)
                                                   if world > 1 else "none (one process)"),
         "collective": collective,
-        "totals_check": {"ok": totals_ok, "frames_reduced": total,
-                         "points": [int(x) for x in totals[:, 0].tolist()],
-                         "how": "after the timed steps, a fresh sum of the rank's per-frame sums, "
-                                "all-reduced over the same backend, equals the totals the steps reduced"},
         "data": "synthetic: device SplitMix64 uniform bytes, seed 0x7A1C" if args.kind == 0
                 else "synthetic: device scene generator (gradients + 6 discs), seed 0x7A1C",
         "config": {"workload": workload_name(args.workload, F, total, world, W, H, T),
@@ -518,7 +569,12 @@ def main():
                                       "the step's launches (zero the sums, hot kernel, epilogue, totals)"),
                      "bytes_per_launch": bytes_per_launch},
     }
-    if not args.no_extras:
+    if args.full:
+        out["totals_check"] = {"ok": totals_ok, "frames_reduced": total,
+                               "points": [int(x) for x in totals[:, 0].tolist()],
+                               "how": "after the timed steps, a fresh sum of the rank's per-frame sums, "
+                                      "all-reduced over the same backend, equals the totals the steps reduced"}
+    if extras:
         out["cold_batch"] = {"cold_batch_ms": round(new_ms, 4), "table_build_ms": round(new_ms - warm_ms, 4),
                        "warm_same_set_ms": round(warm_ms, 4),
                        "host_call_ms": round(new_host_ms, 4),
@@ -532,7 +588,7 @@ def main():
                                "the warmup"}
     if scene is not None:
         out["scene"] = scene
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         n_host = min(F, max(args.cpu_frames_all, args.cpu_frames))
         host = frames[: n_host * fb].cpu().numpy()
         cb, parity = cpu_baseline(args, W, H, ll, T, host, sums.cpu().numpy())

@@ -1,0 +1,278 @@
+// trik_hsv_batch.cpp -- Layer 2 of the C ABI: the batched device API
+// (trik_hsv_*), each entry point its argument checks and then the shared
+// enqueue path (run_sums, or the sensor's core in trik_hsv_sensors.cpp).
+#include "trik_hsv_handle.h"
+
+using namespace trik_hsv;
+
+namespace {
+
+// A device buffer handed to a batched call must be device-accessible memory
+// of the handle's device ("" if so).
+std::string device_buffer_error(const void* p, int dev, const char* what) {
+  if (!p) return "";
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return std::string(what) + " is not device-accessible memory";
+  }
+  if (at.type == hipMemoryTypeUnregistered)
+    return std::string(what) + " is pageable host memory, not device-accessible memory";
+  if (at.type == hipMemoryTypeDevice && at.device != dev)
+    return std::string(what) + " is on device " + std::to_string(at.device) + ", the handle on device " +
+           std::to_string(dev);
+  return "";
+}
+
+// The batch's frames and the output buffer live on the handle's device.
+int32_t check_device(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, const void* out) {
+  if (!b || b->n_frames <= 0) return 0;
+  DeviceGuard dg(h->device);
+  std::string e = device_buffer_error(b->frames, h->device, "frames");
+  if (e.empty()) e = device_buffer_error(out, h->device, "the output buffer");
+  return e.empty() ? 0 : fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+}
+
+int32_t check_batch(const TrikHsvFrameBatch* b) {
+  const std::string e = validate_batch(b);
+  return e.empty() ? 0 : fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+}
+
+int32_t check_handle_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b) {
+  if (!h) return fail(TRIK_IVIDTRANSCODE_EFAIL, "handle is NULL");
+  return check_batch(b);
+}
+
+int32_t check_common(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                     const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n, const void* sums) {
+  int32_t rc = check_handle_batch(h, b);
+  if (rc) return rc;
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES || !ranges)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "n_ranges must be 1..64");
+  if (!sums && b->n_frames > 0) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  return check_device(h, b, sums);
+}
+
+// "ov7670 layout required": sensor names the caller in the message.
+int32_t check_ov7670(const TrikHsvFrameBatch* b, const char* sensor) {
+  if (b->layout == TRIK_HSV_LAYOUT_OV7670) return 0;
+  return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("the ") + sensor + " sensor takes the ov7670 layout (YUV422P)");
+}
+
+// The preview-output geometry of a preview entry point; *pb: bytes of one
+// preview.  `buffers`: every buffer the call needs is there.  The object
+// sensor's call (ball) also checks its sums_pitch and words its errors itself.
+int32_t check_preview_out(const TrikHsvFrameBatch* b, int32_t ow, int32_t oh, int32_t oll, int64_t stride,
+                          bool buffers, int64_t* pb, bool ball = false, int32_t sums_pitch = 1) {
+  if (ow < 0 || oh < 0 || oll < 2 * ow || sums_pitch < 1)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("preview geometry: need out_line_length >= 2*out_width") +
+                                              (ball ? ", sums_pitch >= 1" : ""));
+  *pb = (int64_t)oh * oll;
+  if (b->n_frames > 1 && stride < *pb)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "preview_stride smaller than one preview");
+  if (b->n_frames > 0 && *pb > 0 && !buffers)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, ball ? "previews is NULL" : "NULL buffer");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int32_t trik_hsv_batch_sums(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                       const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n,
+                                       TrikHsvTargetSums* sums, void* stream) {
+  int32_t rc = check_common(h, b, ranges, n, sums);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  return run_sums(h, b, ranges, n, sums, nullptr, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trik_hsv_batch_totals(int32_t n_frames, int32_t n_ranges, const TrikHsvTargetSums* sums,
+                                         TrikHsvTargetSums* totals, void* stream) {
+  if (n_frames < 0 || n_ranges < 1 || n_ranges > TRIK_HSV_MAX_RANGES)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "batch_totals: need n_frames >= 0 and n_ranges 1..64");
+  if (!totals || (n_frames > 0 && !sums)) return fail(TRIK_IVIDTRANSCODE_EFAIL, "batch_totals: NULL buffer");
+  HIP_TRY(launch_totals(n_frames, n_ranges, sums, totals, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_batch_targets(const TrikHsvFrameBatch* b, int32_t n,
+                                          const TrikHsvTargetSums* sums, TrikHsvTarget* targets,
+                                          void* stream) {
+  // only the geometry matters here (no frame bytes are read)
+  if (!b) return fail(TRIK_IVIDTRANSCODE_EFAIL, "batch is NULL");
+  if (b->n_frames < 0 || b->width <= 0 || b->height <= 0 || b->width > 32767 || b->height > 32767)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "batch_targets: need n_frames >= 0 and 0 < width, height <= 32767");
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES) return fail(TRIK_IVIDTRANSCODE_EFAIL, "n_ranges must be 1..64");
+  if (b->n_frames > 0 && (!sums || !targets)) return fail(TRIK_IVIDTRANSCODE_EFAIL, "NULL buffer");
+  HIP_TRY(launch_targets(*b, n, sums, targets, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_process_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                          const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n,
+                                          TrikHsvTargetSums* sums, TrikHsvTarget* targets,
+                                          void* stream) {
+  int32_t rc = check_common(h, b, ranges, n, sums);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  StepOut step;
+  step.targets = targets;
+  return run_sums(h, b, ranges, n, sums, nullptr, s, &step);
+}
+
+extern "C" int32_t trik_hsv_process_batch_totals(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                                 const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n,
+                                                 TrikHsvTargetSums* sums, TrikHsvTarget* targets,
+                                                 TrikHsvTargetSums* totals, void* stream) {
+  int32_t rc = check_common(h, b, ranges, n, sums);
+  if (rc) return rc;
+  if (!totals) return fail(TRIK_IVIDTRANSCODE_EFAIL, "totals is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  rc = check_device(h, b, totals);
+  if (rc) return rc;
+  StepOut step;
+  step.targets = targets;
+  step.totals = totals;
+  return run_sums(h, b, ranges, n, sums, nullptr, s, &step);
+}
+
+extern "C" int32_t trik_hsv_batch_masks(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                        const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n,
+                                        uint8_t* masks, TrikHsvTargetSums* sums, void* stream) {
+  int32_t rc = check_common(h, b, ranges, n, sums);
+  if (rc) return rc;
+  if (n > 8) return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask mode supports at most 8 ranges");
+  if (!masks && b->n_frames > 0) return fail(TRIK_IVIDTRANSCODE_EFAIL, "masks is NULL");
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  return run_sums(h, b, ranges, n, sums, masks, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t trik_hsv_batch_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                          const TRIK_VIDTRANSCODE_CV_InArgsAlg* range,
+                                          const TrikHsvTargetSums* sums, int32_t sums_pitch,
+                                          int32_t out_width, int32_t out_height,
+                                          int32_t out_line_length, uint8_t* previews,
+                                          int64_t preview_stride, void* stream) {
+  int32_t rc = check_common(h, b, range, 1, sums);
+  if (rc) return rc;
+  int64_t pb = 0;
+  rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews != nullptr, &pb, true,
+                         sums_pitch);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0 || pb == 0) return 0;
+  rc = check_device(h, b, previews);
+  if (rc) return rc;
+  return preview_core(h, *b, *range, sums, sums_pitch, out_width, out_height, out_line_length, previews,
+                      preview_stride, s);
+}
+
+extern "C" int32_t trik_hsv_batch_auto_range(const TrikHsvFrameBatch* b, uint16_t* out, void* stream) {
+  int32_t rc = check_batch(b);
+  if (rc) return rc;
+  if (!out && b->n_frames > 0) return fail(TRIK_IVIDTRANSCODE_EFAIL, "out is NULL");
+  HIP_TRY(launch_auto_range(auto_range_args(*b, out), static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_line_batch(const TrikHsvFrameBatch* b, int32_t val_from, int32_t val_to,
+                                       int32_t band_start, int32_t band_stop, TrikHsvTargetSums* sums,
+                                       TrikHsvTarget* targets, void* stream) {
+  int32_t rc = check_batch(b);
+  if (!rc) rc = check_ov7670(b, "line");
+  if (rc) return rc;
+  if (b->n_frames > 0 && !sums) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (b->n_frames == 0) return 0;
+  HIP_TRY(hipMemsetAsync(sums, 0, sizeof(TrikHsvTargetSums) * (size_t)b->n_frames, s));
+  if (b->width == 0 || b->height == 0) {
+    if (targets) HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * (size_t)b->n_frames, s));
+    return 0;
+  }
+  HIP_TRY(launch_line(line_args(*b, val_from, val_to, band_start, band_stop, sums, targets), s));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                         int32_t val_from, int32_t val_to, const TrikHsvTargetSums* sums,
+                                         int32_t out_width, int32_t out_height, int32_t out_line_length,
+                                         uint8_t* previews, int64_t preview_stride, void* stream) {
+  int32_t rc = check_handle_batch(h, b);
+  if (!rc) rc = check_ov7670(b, "line");
+  int64_t pb = 0;
+  if (!rc) rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && sums, &pb);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0 || pb == 0) return 0;
+  rc = check_device(h, b, previews);
+  if (rc) return rc;
+  return line_preview_core(h, *b, line_alg(val_from, val_to), 5, b->width - 5, 1, sums, out_width, out_height,
+                           out_line_length, previews, preview_stride, s);
+}
+
+extern "C" int32_t trik_hsv_blob_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                       const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg* hsv, TrikHsvTarget* targets,
+                                       int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,
+                                       void* stream) {
+  int32_t r = check_handle_batch(h, b);
+  if (!r) r = check_ov7670(b, "multi-blob");
+  if (r) return r;
+  if (!hsv) return fail(TRIK_IVIDTRANSCODE_EFAIL, "hsv is NULL");
+  if (b->width % 32 || b->height % 4) return fail(TRIK_IVIDTRANSCODE_EFAIL, "width % 32 / height % 4");
+  if (b->width > 8192 || blob_max_labels(b->width / 4, b->height / 4) > 30000)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "frame too large for the multi-blob sensor");
+  if (b->n_frames > 0 && !targets) return fail(TRIK_IVIDTRANSCODE_EFAIL, "targets is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0) return 0;
+  r = check_device(h, b, targets);
+  if (r) return r;
+  if (b->width == 0 || b->height == 0) {
+    HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * 8 * (size_t)b->n_frames, s));
+    if (top) HIP_TRY(hipMemsetAsync(top, 0, sizeof(int32_t) * 24 * (size_t)b->n_frames, s));
+    if (n_labels) HIP_TRY(hipMemsetAsync(n_labels, 0, sizeof(int32_t) * (size_t)b->n_frames, s));
+    return 0;
+  }
+  BlobArgs ba;
+  return blob_core(h, *b, blob_range_args(*hsv), targets, top, meta, labels, n_labels, s, ba);
+}
+
+extern "C" int32_t trik_hsv_blob_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                         const uint8_t* meta, const int32_t* top, int32_t out_width,
+                                         int32_t out_height, int32_t out_line_length, uint8_t* previews,
+                                         int64_t preview_stride, void* stream) {
+  int32_t rc = check_handle_batch(h, b);
+  if (!rc) rc = check_ov7670(b, "multi-blob");
+  int64_t pb = 0;
+  if (!rc)
+    rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && meta && top, &pb);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0 || pb == 0) return 0;
+  rc = check_device(h, b, previews);
+  if (rc) return rc;
+  return blob_preview_core(h, *b, meta, top, out_width, out_height, out_line_length, previews, preview_stride, s);
+}
+
+extern "C" int32_t trik_hsv_synth(const TrikHsvFrameBatch* b, int32_t first_frame, int32_t kind,
+                                  uint64_t seed, void* stream) {
+  int32_t rc = check_batch(b);
+  if (rc) return rc;
+  if (kind != 0 && kind != 1) return fail(TRIK_IVIDTRANSCODE_EFAIL, "kind must be 0 or 1");
+  HIP_TRY(launch_synth(*b, const_cast<uint8_t*>(static_cast<const uint8_t*>(b->frames)), first_frame,
+                       kind, seed, static_cast<hipStream_t>(stream)));
+  return 0;
+}

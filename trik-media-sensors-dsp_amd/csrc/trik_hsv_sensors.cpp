@@ -1,0 +1,374 @@
+// trik_hsv_sensors.cpp -- the host side of the operator outputs (previews,
+// line sensors, multi-blob sensor, auto range): the preview geometry, the
+// kernel arguments, and one enqueue core per sensor, shared by process() and
+// the batch API.
+#include <string.h>
+
+#include "trik_hsv_handle.h"
+
+using namespace trik_hsv;
+
+namespace {
+
+// Scale maps of the preview (WSEQ:371-387) for this geometry, uploaded once.
+// col_lo..col_hi: the source columns that write (the line sensor's window).
+// A geometry change (rare) waits for the kernels still reading the old maps
+// and for the upload (the staging is pageable and reused).
+int32_t ensure_maps(TrikCvHandle* h, int w, int hgt, int ow, int oh, hipStream_t s, int col_lo = 0,
+                    int col_hi = 0x7FFFFFFF) {
+  if (h->d_maps && h->maps_key[0] == w && h->maps_key[1] == hgt && h->maps_key[2] == ow &&
+      h->maps_key[3] == oh && h->maps_key[4] == col_lo && h->maps_key[5] == col_hi)
+    return 0;
+  const size_t n = (size_t)w + hgt + ow + oh;
+  h->maps_users.wait_all();  // previous users done
+  h->h_maps.assign(n ? n : 1, 0u);
+  preview_maps(w, hgt, ow, oh, h->h_maps.data(), col_lo, col_hi);
+  // the 2:1 maps (the defaults' 640x480 -> 320x240): preview_rows2_kernel
+  bool rows2 = false;
+  int c0 = 0, c1 = ow;
+  {
+    const uint32_t* last_row = h->h_maps.data() + w + hgt;
+    const uint32_t* last_col = last_row + oh;
+    rows2 = oh > 0 && ow > 0 && (int32_t)last_row[0] >= 0;
+    for (int r = 0; rows2 && r < oh; ++r) rows2 = (int32_t)last_row[r] == (int32_t)last_row[0] + 2 * r;
+    // the written columns: one window [c0, c1) with last_col[c] = 2c + 1, -1 outside
+    while (c0 < ow && (int32_t)last_col[c0] < 0) ++c0;
+    while (c1 > c0 && (int32_t)last_col[c1 - 1] < 0) --c1;
+    for (int c = 0; rows2 && c < ow; ++c)
+      rows2 = (c >= c0 && c < c1) ? (int32_t)last_col[c] == 2 * c + 1 : (int32_t)last_col[c] < 0;
+    h->maps_rows2 = rows2 ? (int32_t)last_row[0] : -1;
+  }
+  h->maps_rows2_c0 = c0;
+  h->maps_rows2_c1 = c1;
+  // The object sensors' 8 guide lines (draw_guides, WSEQ:136-166,471-485) as
+  // output pixels, one bit each, 8 per byte along a row, behind the maps: the
+  // 2:1 row kernel writes them as it writes the preview, so the overlay only
+  // draws the target circle.  The same points and clamping as Canvas::px.
+  h->maps_guides = 0;
+  if (rows2 && ow % 8 == 0 && w > 0 && hgt > 0) {
+    const size_t gpr = (size_t)ow / 8, words = ((size_t)oh * gpr + 3) / 4;
+    h->h_maps.resize(n + words, 0u);
+    uint8_t* bits = reinterpret_cast<uint8_t*>(h->h_maps.data() + n);
+    const uint32_t* wi2wo = h->h_maps.data();
+    const uint32_t* hi2ho = wi2wo + w;
+    const auto px = [&](int col, int row) {
+      const int sc = col < 0 ? 0 : (col > w - 1 ? w - 1 : col);
+      const int sr = row < 0 ? 0 : (row > hgt - 1 ? hgt - 1 : row);
+      const uint32_t oc = wi2wo[sc], orow = hi2ho[sr];
+      if (oc < (uint32_t)ow && orow < (uint32_t)oh) bits[orow * gpr + oc / 8] |= (uint8_t)(1u << (oc % 8));
+    };
+    const int step = hgt / 6, hh = hgt / 2, hw = w / 2;
+    for (int k = 0; k < 8 * 100; ++k) {
+      const int line = k / 100, adj = k % 100, off = (line & 3) < 2 ? ((line & 3) - 2) : ((line & 3) - 1);
+      if (line < 4) {
+        px(hw + off * step, hh - adj);
+        px(hw + off * step, hh + adj);
+      } else {
+        px(hw - adj, hh + off * step);
+        px(hw + adj, hh + off * step);
+      }
+    }
+    h->maps_guides = 1;
+  }
+  const size_t total = h->h_maps.size();
+  const int32_t rc = grow(h->d_maps, h->d_maps_cap, sizeof(uint32_t) * total);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h->d_maps, h->h_maps.data(), sizeof(uint32_t) * total, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));  // h_maps is pageable and reused
+  h->maps_key[0] = w; h->maps_key[1] = hgt; h->maps_key[2] = ow; h->maps_key[3] = oh;
+  h->maps_key[4] = col_lo; h->maps_key[5] = col_hi;
+  // the line overlays' output pixels (line_overlay_kernel, LSEQ:419-474): a
+  // column map with steps of 0 or 1 sends any source interval to one interval
+  const uint32_t* wi2wo = h->h_maps.data();
+  const uint32_t* hi2ho = wi2wo + w;
+  bool step1 = w > 0 && hgt > 0;
+  for (int c = 1; step1 && c < w; ++c) step1 = wi2wo[c] - wi2wo[c - 1] <= 1u;
+  h->maps_ovl_ok = step1 ? 1 : 0;
+  bool half = step1;
+  for (int c = 0; half && c < w; ++c) half = wi2wo[c] == (uint32_t)c >> 1;
+  h->maps_ovl_half = half ? 1 : 0;
+  if (step1) {
+    const auto cl = [](int v, int n) { return v < 0 ? 0 : (v > n - 1 ? n - 1 : v); };
+    const int hw = w / 2, hh = hgt / 2, step = 40;
+    const int cols[4] = {hw - step, hw + step, hw - 2 * step, hw + 2 * step};
+    for (int j = 0; j < 4; ++j) h->maps_ovl_mag[j] = (int32_t)wi2wo[cl(cols[j], w)];
+    h->maps_ovl_band[0] = (int32_t)hi2ho[cl(hh, hgt)];
+    h->maps_ovl_band[1] = (int32_t)hi2ho[cl(hh + 2 * step, hgt)];
+    h->maps_ovl_c_lo = (int32_t)wi2wo[0];
+    h->maps_ovl_c_hi = (int32_t)wi2wo[w - 1];
+  }
+  return 0;
+}
+
+// The preview kernels' arguments on the handle's current maps.  The range is
+// the all-zero one (the multi-blob preview detects by metapixel);
+// preview_tables sets it wherever a range applies.
+PreviewArgs preview_args(const TrikCvHandle* h, const TrikHsvFrameBatch& b, int ow, int oh, int oll,
+                         uint8_t* previews, int64_t stride) {
+  PreviewArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length; a.layout = b.layout;
+  a.range = PackedRange{0, 0, 0};
+  a.aligned4 = aligned4(b) && (reinterpret_cast<uintptr_t>(previews) & 3) == 0 &&
+               (b.n_frames <= 1 || (stride & 3) == 0) && (oll & 3) == 0;
+  a.out_w = ow; a.out_h = oh; a.out_ll = oll;
+  a.previews = previews;
+  a.preview_stride = stride;
+  a.wi2wo = h->d_maps;
+  a.hi2ho = a.wi2wo + b.width;
+  a.last_row = reinterpret_cast<const int32_t*>(a.hi2ho + b.height);
+  a.last_col = a.last_row + oh;
+  a.rows2_first = h->maps_rows2;
+  if (h->maps_guides) a.guide_bits = reinterpret_cast<const uint8_t*>(h->d_maps + b.width + b.height + ow + oh);
+  a.rows2_c0 = h->maps_rows2_c0;
+  a.rows2_c1 = h->maps_rows2_c1;
+  a.ovl_ok = h->maps_ovl_ok;
+  a.ovl_half = h->maps_ovl_half;
+  for (int j = 0; j < 4; ++j) a.ovl_mag[j] = h->maps_ovl_mag[j];
+  a.ovl_band[0] = h->maps_ovl_band[0];
+  a.ovl_band[1] = h->maps_ovl_band[1];
+  a.ovl_c_lo = h->maps_ovl_c_lo;
+  a.ovl_c_hi = h->maps_ovl_c_hi;
+  return a;
+}
+
+// The preview's detection range compiled as a single-range table set.
+int32_t preview_tables(TrikCvHandle* h, PreviewArgs& pa, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
+                       hipStream_t s, TableSet** set) {
+  int32_t rc = acquire_tables(h, &range, 1, s, set);
+  if (rc) return rc;
+  pa.range = pack_range(range);
+  pa.tables = (*set)->d_stripe;
+  pa.hue_free = !(*set)->detect.empty() && (*set)->detect[0] != kDetectFull ? 1 : 0;
+  return 0;
+}
+
+// LSEQ:391-414: hue and saturation bounds fixed at 0..255 (unscaled), value
+// scaled as the object sensor's.
+uint32_t scale_val(int v) {
+  const int s = (v * 255) / 100;
+  return (uint32_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
+}
+
+// BitmapBuilder::run's range update (cv_bitmap_builder_reference.hpp:110-130):
+// from/to around the centre (hue wraps, sat/val clip), scaled as the webcam's,
+// then resetHsvRange (:62-77).
+int wrap_value(int v, int adj, int lo, int hi) {  // makeValueWrap, stdcpp.hpp
+  v += adj;
+  while (v > hi) v -= hi - lo + 1;
+  while (v < lo) v += hi - lo + 1;
+  return v;
+}
+int clip_value(int v, int adj, int lo, int hi) {  // makeValueRange, stdcpp.hpp
+  v += adj;
+  return v > hi ? hi : (v < lo ? lo : v);
+}
+
+}  // namespace
+
+// The line sensor's range in the object sensor's terms: hue 0..359 and
+// saturation 0..100 scale to the full 0..255 bytes LSEQ:391-396 fixes.
+TRIK_VIDTRANSCODE_CV_InArgsAlg trik_hsv::line_alg(int val_from, int val_to) {
+  TRIK_VIDTRANSCODE_CV_InArgsAlg r;
+  memset(&r, 0, sizeof r);
+  r.detectHueFrom = 0;
+  r.detectHueTo = 359;
+  r.detectSatFrom = 0;
+  r.detectSatTo = 100;
+  r.detectValFrom = (uint8_t)val_from;
+  r.detectValTo = (uint8_t)val_to;
+  return r;
+}
+
+LineArgs trik_hsv::line_args(const TrikHsvFrameBatch& b, int val_from, int val_to, int band_start, int band_stop,
+                             TrikHsvTargetSums* sums, TrikHsvTarget* targets) {
+  LineArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  a.val_lo = scale_val(val_from);
+  a.val_hi = scale_val(val_to);
+  a.band_start = band_start;
+  a.band_stop = band_stop;
+  a.sums = sums;
+  a.targets = targets;
+  return a;
+}
+
+TRIK_VIDTRANSCODE_CV_InArgsAlg trik_hsv::blob_range_args(const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg& a) {
+  TRIK_VIDTRANSCODE_CV_InArgsAlg r;
+  memset(&r, 0, sizeof r);
+  r.detectHueFrom = (uint16_t)wrap_value(a.detectHue, -(int)a.detectHueTol, 0, 359);
+  r.detectHueTo = (uint16_t)wrap_value(a.detectHue, (int)a.detectHueTol, 0, 359);
+  r.detectSatFrom = (uint8_t)clip_value(a.detectSat, -(int)a.detectSatTol, 0, 100);
+  r.detectSatTo = (uint8_t)clip_value(a.detectSat, (int)a.detectSatTol, 0, 100);
+  r.detectValFrom = (uint8_t)clip_value(a.detectVal, -(int)a.detectValTol, 0, 100);
+  r.detectValTo = (uint8_t)clip_value(a.detectVal, (int)a.detectValTol, 0, 100);
+  return r;  // then the same scaling and wrap packing (WSEQ:425-445 = BMB:62-77)
+}
+
+AutoRangeArgs trik_hsv::auto_range_args(const TrikHsvFrameBatch& b, uint16_t* out) {
+  AutoRangeArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length; a.layout = b.layout;
+  auto_range_zone(b.width, b.height, a.c_lo, a.c_hi, a.r_lo, a.r_hi);
+  a.aligned4 = aligned4(b);
+  a.out = out;
+  return a;
+}
+
+namespace {
+
+// Scratch for n frames of W x H.  Stream s waits (device side) for the
+// handle's earlier multi-blob work on other streams, which used the same
+// scratch; growing it (a larger batch) waits for that work on the host.
+int32_t ensure_blob_scratch(TrikCvHandle* h, int n, int w, int hgt, hipStream_t s) {
+  const size_t bw = (size_t)(w / 4), bh = (size_t)(hgt / 4), nn = (size_t)(n > 0 ? n : 1);
+  const size_t ml = (size_t)blob_max_labels((int)bw, (int)bh);
+  if (nn * (bw * bh > 0 ? bw * bh : 1) > h->d_meta_cap || nn * 3 * ml * sizeof(int32_t) > h->d_blob_stats_cap ||
+      nn * 24 * sizeof(int32_t) > h->d_blob_top_cap || nn * 8 * sizeof(TrikHsvTarget) > h->d_blob_targets_cap)
+    h->blob_users.wait_all();
+  HIP_TRY(h->blob_users.order_after(s));
+  int32_t r = grow(h->d_meta, h->d_meta_cap, nn * (bw * bh > 0 ? bw * bh : 1));
+  // the clusterer's own statistics: zero when allocated, and every clusterer
+  // launch leaves the labels it used zero again (blob_ccl_kernel).  The
+  // capacity counts only once the zeroing is enqueued, and a failed clusterer
+  // launch (which may leave labels non-zero) marks the buffer dirty: the next
+  // call zeroes it whole.
+  const size_t stats_bytes = nn * 3 * ml * sizeof(int32_t);
+  if (!r && (stats_bytes > h->d_blob_stats_cap || h->blob_stats_dirty)) {
+    if (stats_bytes > h->d_blob_stats_cap) r = grow(h->d_blob_stats, h->d_blob_stats_cap, stats_bytes);
+    if (!r) {
+      const hipError_t e = hipMemsetAsync(h->d_blob_stats, 0, h->d_blob_stats_cap, s);
+      if (e != hipSuccess) {
+        h->blob_stats_dirty = true;
+        return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("hipMemsetAsync(blob stats): ") + hipGetErrorString(e));
+      }
+      h->blob_stats_dirty = false;
+    }
+  }
+  if (!r) r = grow(h->d_blob_top, h->d_blob_top_cap, nn * 24 * sizeof(int32_t));
+  if (!r) r = grow(h->d_blob_targets, h->d_blob_targets_cap, nn * 8 * sizeof(TrikHsvTarget));
+  return r;
+}
+
+// Compiles the range's tables (cached per handle) and fills the kernel args.
+int32_t blob_args(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
+                  TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,
+                  hipStream_t s, BlobArgs& a, TableSet** set) {
+  int32_t rc = acquire_tables(h, &range, 1, s, set);
+  if (rc) return rc;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  a.range = pack_range(range);
+  a.tables = (*set)->d_stripe;
+  a.aligned4 = aligned4(b);
+  a.meta = meta ? meta : h->d_meta;
+  a.labels = labels;
+  a.stats = h->d_blob_stats;
+  a.max_labels = (int32_t)blob_max_labels(b.width / 4, b.height / 4);
+  a.targets = targets ? targets : h->d_blob_targets;
+  a.top = top ? top : h->d_blob_top;
+  a.n_labels = n_labels;
+  return 0;
+}
+
+// The multi-blob sensor: the metapixel bitmap on the chroma-run tables of the
+// sticky range when the hot-kernel setting allows it (AUTO: batches of at
+// least TRIK_HSV_CHROMA_MIN_PIXELS whose exact-path share is low), else the
+// stripe-arithmetic kernel inside launch_blob; then the clusterer.
+int32_t run_blob(TrikCvHandle* h, BlobArgs& ba, TableSet& t, hipStream_t s) {
+  const bool big = (int64_t)ba.n_frames * ba.width * ba.height >= (int64_t)TRIK_HSV_CHROMA_MIN_PIXELS;
+  int32_t rc = 0;
+  const HotPlan plan = plan_hot(h, t, 0, 1, big, h->hot.load() != TRIK_HSV_HOT_GENERIC && blob_chroma_ok(ba), s, &rc);
+  if (rc) return rc;
+  ba.meta_ready = 0;
+  h->pending_set = nullptr;
+  h->hot_groups.assign(1, TRIK_HSV_HOT_STRIPE);
+  if (plan == kPlanChroma) {
+    HIP_TRY(launch_blob_meta_chroma(ba, t.d_chroma, t.d_tables, s));
+    ba.meta_ready = 1;
+    h->hot_groups[0] = TRIK_HSV_HOT_CHROMA;
+  } else if (plan == kPlanGated) {  // both bitmap kernels, the device runs one (see run_sums)
+    BlobArgs bc = ba;
+    bc.gate = ba.gate = &t.d_chroma[0].flagged_cost;
+    bc.gate_max = ba.gate_max = kChromaMaxCost;
+    bc.gate_le = 1;
+    ba.gate_le = 0;
+    HIP_TRY(launch_blob_meta_chroma(bc, t.d_chroma, t.d_tables, s));
+    h->pending_set = &t;
+    h->hot_groups[0] = -TRIK_HSV_HOT_STRIPE;
+  }
+  const int e = launch_blob(ba, s);
+  if (e != hipSuccess) {
+    h->blob_stats_dirty = true;  // (the clusterer may not have restored its statistics to zero)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("launch_blob: ") + hipGetErrorString((hipError_t)e));
+  }
+  return 0;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// One enqueue path per sensor
+// ---------------------------------------------------------------------------
+// the preview kernel writes every byte of each preview, zeros included (WFXNS:234)
+int32_t trik_hsv::preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
+                               const TRIK_VIDTRANSCODE_CV_InArgsAlg& range, const TrikHsvTargetSums* sums,
+                               int sums_pitch, int ow, int oh, int oll, uint8_t* previews, int64_t stride,
+                               hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+  if (rc) return rc;
+  PreviewArgs pa = preview_args(h, b, ow, oh, oll, previews, stride);
+  TableSet* set = nullptr;
+  rc = preview_tables(h, pa, range, s, &set);
+  if (rc) return rc;
+  HIP_TRY(launch_preview(pa, sums, sums_pitch, s));
+  return note_uses(h, set, true, s);
+}
+
+int32_t trik_hsv::line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
+                                    const TRIK_VIDTRANSCODE_CV_InArgsAlg& table_range, int col_lo, int col_hi,
+                                    int band, const TrikHsvTargetSums* sums, int ow, int oh, int oll,
+                                    uint8_t* previews, int64_t stride, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s, col_lo, col_hi);
+  if (rc) return rc;
+  PreviewArgs pa = preview_args(h, b, ow, oh, oll, previews, stride);
+  TableSet* set = nullptr;
+  rc = preview_tables(h, pa, table_range, s, &set);
+  if (rc) return rc;
+  HIP_TRY(launch_line_preview(pa, sums, band, s));
+  return note_uses(h, set, true, s);
+}
+
+int32_t trik_hsv::blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
+                            const TRIK_VIDTRANSCODE_CV_InArgsAlg& range, TrikHsvTarget* targets, int32_t* top,
+                            uint8_t* meta, uint16_t* labels, int32_t* n_labels, hipStream_t s, BlobArgs& ba) {
+  int32_t r = ensure_blob_scratch(h, b.n_frames, b.width, b.height, s);
+  if (r) return r;
+  TableSet* set = nullptr;
+  r = blob_args(h, b, range, targets, top, meta, labels, n_labels, s, ba, &set);
+  if (r) return r;
+  r = run_blob(h, ba, *set, s);
+  if (r) return r;
+  return note_uses(h, set, false, s, &h->blob_users);
+}
+
+int32_t trik_hsv::blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta,
+                                    const int32_t* top, int ow, int oh, int oll, uint8_t* previews, int64_t stride,
+                                    hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+  if (rc) return rc;
+  PreviewArgs pa = preview_args(h, b, ow, oh, oll, previews, stride);
+  pa.meta = meta;
+  HIP_TRY(launch_preview_body(pa, s));
+  HIP_TRY(launch_blob_overlay(pa, top, s));
+  return note_uses(h, nullptr, true, s);
+}

@@ -8,6 +8,8 @@ batched API (trik_hsv_blob_batch / _preview) and the XDAIS quartet
 import numpy as np
 import pytest
 
+from blob_patterns import check_frame
+
 pytestmark = pytest.mark.gpu
 
 RED = (0, 20, 80, 20, 50, 50)
@@ -37,13 +39,7 @@ def _frames(oracle_mod, w, h, ll, cases):
 
 
 def _check(oracle_mod, res, i, fr, w, h, ll, rng_hsv, what):
-    ref = oracle_mod.blob_run(fr, w, h, ll, hsv=rng_hsv, preview=False)
-    assert ref["rc"] == 0
-    assert np.array_equal(res["meta"][i].cpu().numpy(), ref["meta"]), what
-    assert np.array_equal(res["labels"][i].cpu().numpy().view(np.uint16), ref["labels"]), what
-    assert int(res["n_labels"][i]) == ref["n_labels"], what
-    assert np.array_equal(res["top"][i].cpu().numpy(), ref["top"]), what
-    assert np.array_equal(res["targets"][i, :, :3].cpu().numpy(), ref["targets"]), what
+    check_frame(res, i, oracle_mod.blob_run(fr, w, h, ll, hsv=rng_hsv, preview=False), what)
 
 
 # (w, h, ll): VGA, 320x240 with a padded line, bw not a multiple of 64 (K = 2),
@@ -247,13 +243,16 @@ def test_blob_stats_clean_across_geometries(hsv, oracle_mod):
     buffer is not cleared per batch -- it is zeroed when allocated and every
     clusterer wave zeroes the labels it used before it ends -- so each batch
     here runs on what the previous one (another layout, packed or three-int
-    statistics) left behind.  1024 x 1024 takes the unpacked statistics
-    (size, sum x, sum y do not fit 63 bits together)."""
+    statistics) left behind.  1024 x 1024 is still packed (17 + 23 + 23 = 63
+    bits; its sizes are read from memory in the top-8 passes, bw * bh = 65536);
+    1056 x 1024 takes the unpacked statistics (17 + 24 + 24 bits: size, sum x,
+    sum y do not fit 63 bits together)."""
     import torch
 
     seq = [((640, 480, 640), [("meta", 71, 0.5), ("meta", 72, 0.75)]),
            ((1024, 1024, 1024), [("meta", 73, 0.5), ("scene", 74, 0.02)]),
            ((320, 240, 352), [("scene", 75, 0.03), ("meta", 76, 0.3)]),
+           ((1056, 1024, 1056), [("meta", 80, 0.5), ("meta", 81, 0.2)]),
            ((640, 480, 640), [("meta", 77, 0.75), ("meta", 78, 0.1)]),
            ((1024, 1024, 1024), [("meta", 79, 0.3)])]
     det = hsv.Detector()

@@ -202,6 +202,22 @@ typedef struct TRIK_VIDTRANSCODE_CV_OV7670_OutArgsAlg {
   uint16_t detectValTolerance;
 } TRIK_VIDTRANSCODE_CV_OV7670_OutArgsAlg;
 
+/* The ov7670 MxN colour-grid sensor's InArgsAlg and OutArgsAlg (MPUB =
+ * trik/ov7670/mxn_sensor/trik_vidtranscode_cv.h:49-67), field names as the
+ * reference's.  The names are crossed there (its run() assigns widthM to the
+ * grid's height and heightN to its width): widthM is the number of cell ROWS
+ * (a cell is inputHeight / widthM rows high), heightN the number of cell
+ * COLUMNS (inputWidth / heightN columns wide).  outColor[i * heightN + j] is
+ * the 0x00RRGGBB colour of the cell in row i, column j. */
+typedef struct TRIK_VIDTRANSCODE_CV_MXN_InArgsAlg {
+  int32_t widthM;  /* cell rows */
+  int32_t heightN; /* cell columns */
+} TRIK_VIDTRANSCODE_CV_MXN_InArgsAlg;
+
+typedef struct TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg {
+  int32_t outColor[100];
+} TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg;
+
 /* XDM1_SingleBufDesc */
 typedef struct TRIK_XDM1_SingleBufDesc {
   int8_t* buf;
@@ -249,6 +265,16 @@ typedef struct TRIK_VIDTRANSCODE_CV_OV7670_OutArgs { /* OPUB:83-86 */
   TRIK_IVIDTRANSCODE_OutArgs base;
   TRIK_VIDTRANSCODE_CV_OV7670_OutArgsAlg alg;
 } TRIK_VIDTRANSCODE_CV_OV7670_OutArgs;
+
+typedef struct TRIK_VIDTRANSCODE_CV_MXN_InArgs { /* MPUB:54-57 */
+  TRIK_IVIDTRANSCODE_InArgs base;
+  TRIK_VIDTRANSCODE_CV_MXN_InArgsAlg alg;
+} TRIK_VIDTRANSCODE_CV_MXN_InArgs;
+
+typedef struct TRIK_VIDTRANSCODE_CV_MXN_OutArgs { /* MPUB:64-67 */
+  TRIK_IVIDTRANSCODE_OutArgs base;
+  TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg alg;
+} TRIK_VIDTRANSCODE_CV_MXN_OutArgs;
 
 /* XDM1_AlgBufInfo subset filled by GETSTATUS/GETBUFINFO (WFXNS:287-297) */
 typedef struct TRIK_XDM1_AlgBufInfo {
@@ -318,6 +344,27 @@ int32_t TRIK_VIDTRANSCODE_CV_create_webcam_line(const TRIK_VIDTRANSCODE_CV_Param
  * mark per target).  Frames up to 2048x2048 (the reference: 640x480). */
 int32_t TRIK_VIDTRANSCODE_CV_create_ov7670(const TRIK_VIDTRANSCODE_CV_Params* params,
                                            TRIK_VIDTRANSCODE_CV_Handle* out_handle);
+
+/* The quartet for the ov7670 MxN colour-grid sensor's codec (trik/ov7670/
+ * mxn_sensor: BallDetector<YUV422P, RGB565X> of include/internal/
+ * cv_ball_detector_seqpass.hpp -- MSEQ -- behind the ov7670 object sensor's
+ * glue).  params == NULL takes that glue's defaults (YUV422P in, RGB565X
+ * out).  process() then takes TRIK_VIDTRANSCODE_CV_MXN_InArgs and
+ * TRIK_VIDTRANSCODE_CV_MXN_OutArgs (size fields checked).  The frame is split
+ * into widthM rows x heightN columns of cells (steps are truncating
+ * divisions; pixels right of or below the last cell belong to no cell); each
+ * cell's pixels are counted in a 32 x 4 x 4 histogram of (H >> 3, S >> 6,
+ * V >> 6), the bin that first reaches the largest count in the cell's raster
+ * order wins, and outColor[k] is that bin's colour (trik_hsv_mxn_color).
+ * outColor past widthM * heightN is left untouched.  The preview is every
+ * source pixel through the scale maps, then a 20 x 20 square of each cell's
+ * colour at the cell's top-left corner, in cell order (MSEQ:328-366, 609-618).
+ * The one divergence: the reference does not check the grid (0 divides by
+ * zero, more than 100 cells overrun outColor, widthM is cut to 8 bits); here
+ * widthM < 1, heightN < 1 or widthM * heightN > 100 makes process() return
+ * IVIDTRANSCODE_EFAIL with nothing written to outColor. */
+int32_t TRIK_VIDTRANSCODE_CV_create_mxn(const TRIK_VIDTRANSCODE_CV_Params* params,
+                                        TRIK_VIDTRANSCODE_CV_Handle* out_handle);
 
 /* Replaces TRIK_VIDTRANSCODE_CV_free (WFXNS:114-136). */
 int32_t TRIK_VIDTRANSCODE_CV_delete(TRIK_VIDTRANSCODE_CV_Handle handle);
@@ -399,15 +446,16 @@ typedef struct TRIK_IVIDTRANSCODE_Fxns {
 
 /* The webcam object sensor's tables (WFXNS:36-66); IALG is the same table
  * as FXNS.ialg (the reference aliases the two symbols on TI toolchains and
- * duplicates them elsewhere, as here).  The other three codecs of this library
+ * duplicates them elsewhere, as here).  The other four codecs of this library
  * (one DSP server each in the reference, all named TRIK_VIDTRANSCODE_CV_FXNS
- * there): the ov7670 object sensor, the ov7670 line sensor and the webcam
- * line sensor. */
+ * there): the ov7670 object sensor, the ov7670 line sensor, the webcam line
+ * sensor and the ov7670 MxN sensor. */
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_FXNS;
 extern TRIK_IALG_Fxns TRIK_VIDTRANSCODE_CV_IALG;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_OV7670_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_LINE_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS;
+extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_MXN_FXNS;
 
 /* The webcam object sensor's IALG functions (WFXNS:85-166), also reachable
  * through the tables.  alloc asks for one persistent external record (the
@@ -617,6 +665,29 @@ int32_t trik_hsv_blob_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvF
                               const uint8_t* meta_dev, const int32_t* top_dev, int32_t out_width,
                               int32_t out_height, int32_t out_line_length, uint8_t* previews_dev,
                               int64_t preview_stride, void* hip_stream);
+
+/* The ov7670 MxN colour-grid sensor for N ov7670 frames:
+ * rows_m x cols_n cells per frame (rows_m = InArgs widthM, cols_n = heightN;
+ * 1 <= rows_m, 1 <= cols_n, rows_m * cols_n <= 100, else the call fails and
+ * writes nothing):
+ *   colors_dev  [N][rows_m * cols_n] int32: OutArgs outColor of each frame;
+ *   bins_dev    optional [N][rows_m * cols_n] uint16: the winning bin,
+ *               h << 4 | s << 2 | v with h = H >> 3, s = S >> 6, v = V >> 6.
+ * Stream-ordered; scratch lives in the handle. */
+int32_t trik_hsv_mxn_batch(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch, int32_t rows_m,
+                           int32_t cols_n, int32_t* colors_dev, uint16_t* bins_dev, void* hip_stream);
+
+/* Its previews for N frames from colors_dev of trik_hsv_mxn_batch
+ * (MSEQ:328-366, 609-618): zero fill, every source pixel, the cells' squares. */
+int32_t trik_hsv_mxn_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch, int32_t rows_m,
+                             int32_t cols_n, const int32_t* colors_dev, int32_t out_width, int32_t out_height,
+                             int32_t out_line_length, uint8_t* previews_dev, int64_t preview_stride,
+                             void* hip_stream);
+
+/* The MxN sensor's colour of histogram bin (h_bin 0..31, s_bin 0..3, v_bin
+ * 0..3): HSVtoRGB(8 h_bin, 64 s_bin, 64 v_bin) of MSEQ:480-517 as 0x00RRGGBB
+ * (0 for a bin out of range).  Host code: a table built once, no GPU call. */
+uint32_t trik_hsv_mxn_color(int32_t h_bin, int32_t s_bin, int32_t v_bin);
 
 /* Fill batch->frames (device, writable) with synthetic frames; frame i of the
  * batch is global frame first_frame + i.  kind 0 = uniform random bytes,

@@ -11,6 +11,9 @@
               (2 B/px) once.  line_preview: its 320x240 previews.
   blob        trik_hsv_blob_batch: 4096 x 640x480 ov7670 frames through the
               multi-blob sensor (metapixel bitmap + clusterer + 8 targets).
+  mxn         trik_hsv_mxn_batch: the MxN colour-grid sensor over the same
+              ov7670 frames at 3x3 and 10x10 cells, scene and uniform random
+              bytes; algorithmic bytes = both planes once, as the line row.
   process     one host frame through the XDAIS quartet (H2D + kernels + D2H,
               PCIe-inclusive latency per frame), with preview and auto range.
 
@@ -110,7 +113,21 @@ def main():
                    "achieved_GBs": round(lf * lfb / (bl_ms / 1e3) / 1e9, 1),
                    "hbm_frac": round(lf * lfb / (bl_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                    "note": "bitmap (blob_chroma_meta_kernel for large batches, else blob_meta_kernel) + blob_ccl_kernel (one wave per frame)"}
+    # the MxN colour-grid sensor over the same bytes as the line row (scene
+    # frames), then over uniform random bytes; colours only, no preview
+    out["mxn"] = {"frames": lf, "bytes_algorithmic": lf * lfb,
+                  "note": "mxn_hist_kernel, one workgroup per (frame, cell); beside the line row's pass over the "
+                          "same planes"}
     ldev_host = ldev[: 8 * lfb].cpu().numpy()
+    for kind, name in ((1, "scene"), (0, "uniform")):
+        if kind == 0:
+            trik_hsv.synth(ldev, W, H, W, trik_hsv.LAYOUT_OV7670, 0, 0x7A1C)
+        for m, n in ((3, 3), (10, 10)):
+            ms = timed(lambda: det.mxn_batch(ldev, W, H, W, m, n), stream, args.iters)
+            out["mxn"][f"{name}_{m}x{n}"] = {"ms": round(ms, 4), "Mframes_per_s": round(lf / ms / 1e3, 3),
+                                             "achieved_GBs": round(lf * lfb / (ms / 1e3) / 1e9, 1),
+                                             "hbm_frac": round(lf * lfb / (ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+                                             "over_line": round(ms / ln_ms, 2)}
     del ldev
 
     s = trik_hsv.ObjectSensor()

@@ -267,6 +267,64 @@ extern "C" int32_t trik_hsv_blob_preview(TRIK_VIDTRANSCODE_CV_Handle h, const Tr
   return blob_preview_core(h, *b, meta, top, out_width, out_height, out_line_length, previews, preview_stride, s);
 }
 
+extern "C" int32_t trik_hsv_mxn_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, int32_t rows_m,
+                                      int32_t cols_n, int32_t* colors, uint16_t* bins, void* stream) {
+  int32_t r = check_handle_batch(h, b);
+  if (!r) r = check_ov7670(b, "MxN");
+  if (r) return r;
+  const std::string e = mxn_grid_error(rows_m, cols_n);
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  if (b->n_frames > 0 && !colors) return fail(TRIK_IVIDTRANSCODE_EFAIL, "colors is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0) return 0;
+  r = check_device(h, b, colors);
+  if (r) return r;
+  if (b->width == 0 || b->height == 0) {  // every cell is empty: bin (0, 0, 0), colour 0
+    const size_t cells = (size_t)b->n_frames * rows_m * cols_n;
+    HIP_TRY(hipMemsetAsync(colors, 0, sizeof(int32_t) * cells, s));
+    if (bins) HIP_TRY(hipMemsetAsync(bins, 0, sizeof(uint16_t) * cells, s));
+    return 0;
+  }
+  return mxn_core(h, *b, rows_m, cols_n, colors, bins, s);
+}
+
+extern "C" int32_t trik_hsv_mxn_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, int32_t rows_m,
+                                        int32_t cols_n, const int32_t* colors, int32_t out_width,
+                                        int32_t out_height, int32_t out_line_length, uint8_t* previews,
+                                        int64_t preview_stride, void* stream) {
+  int32_t rc = check_handle_batch(h, b);
+  if (!rc) rc = check_ov7670(b, "MxN");
+  if (rc) return rc;
+  const std::string e = mxn_grid_error(rows_m, cols_n);
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  int64_t pb = 0;
+  rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && colors, &pb);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0 || pb == 0) return 0;
+  rc = check_device(h, b, previews);
+  if (rc) return rc;
+  if (b->width == 0 || b->height == 0) {  // no pixel to write: the zero fill alone
+    for (int32_t f = 0; f < b->n_frames; ++f)
+      HIP_TRY(hipMemsetAsync(previews + (int64_t)f * (b->n_frames > 1 ? preview_stride : 0), 0, (size_t)pb, s));
+    return 0;
+  }
+  return mxn_preview_core(h, *b, rows_m, cols_n, colors, out_width, out_height, out_line_length, previews,
+                          preview_stride, s);
+}
+
+extern "C" uint32_t trik_hsv_mxn_color(int32_t h_bin, int32_t s_bin, int32_t v_bin) {
+  if (h_bin < 0 || h_bin > 31 || s_bin < 0 || s_bin > 3 || v_bin < 0 || v_bin > 3) {
+    fail(TRIK_IVIDTRANSCODE_EFAIL, "mxn_color: bins are h 0..31, s 0..3, v 0..3");
+    return 0;
+  }
+  return mxn_color_table()[(h_bin << 4) | (s_bin << 2) | v_bin];
+}
+
 extern "C" int32_t trik_hsv_synth(const TrikHsvFrameBatch* b, int32_t first_frame, int32_t kind,
                                   uint64_t seed, void* stream) {
   int32_t rc = check_batch(b);

@@ -24,7 +24,11 @@
 // kAlgoWLine: the webcam line sensor (LineDetector<YUV422, RGB565X> of
 // trik/webcam/line_sensor/include/internal/cv_line_detector_seqpass.hpp --
 // LSEQW -- with the webcam glue, a 240x320 default output as the line glues).
-enum Algo { kAlgoBall = 0, kAlgoLine = 1, kAlgoBlob = 2, kAlgoWLine = 3 };
+// kAlgoMxn: the ov7670 MxN colour-grid sensor (BallDetector<YUV422P, RGB565X>
+// of trik/ov7670/mxn_sensor/include/internal/cv_ball_detector_seqpass.hpp --
+// MSEQ -- behind the ov7670 object sensor's glue: YUV422P input, a 320x240
+// default output).
+enum Algo { kAlgoBall = 0, kAlgoLine = 1, kAlgoBlob = 2, kAlgoWLine = 3, kAlgoMxn = 4 };
 
 // ---------------------------------------------------------------------------
 // Handle
@@ -286,6 +290,10 @@ struct TrikCvHandle {
   TrikHsvTarget* d_blob_targets = nullptr;
   size_t d_blob_targets_cap = 0;
   StreamUses blob_users;  // calls that wrote the multi-blob scratch
+  // MxN sensor: the colour table's device copy (uploaded once, then only
+  // read) and process()'s cell colours (used on the handle's stream only)
+  uint32_t* d_mxn_table = nullptr;
+  int32_t* d_mxn_colors = nullptr;
   StreamMarks marks;      // the events the StreamUses lists point at (freed last)
 };
 
@@ -385,6 +393,17 @@ int32_t blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRA
 // its preview: set metapixels, guide lines, target marks
 int32_t blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta, const int32_t* top,
                           int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);
+
+// the MxN sensor: cell colours (and winning bins when not NULL) of rows_m x
+// cols_n cells per frame; rows_m, cols_n validated by the caller (mxn_grid_error)
+int32_t mxn_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int cols_n, int32_t* colors,
+                 uint16_t* bins, hipStream_t s);
+// its preview: every source pixel, then the cells' 20x20 squares in cell order
+int32_t mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int cols_n, const int32_t* colors,
+                         int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);
+// "" when 1 <= rows_m, 1 <= cols_n and rows_m * cols_n <= 100 (OutArgs holds
+// 100 colours; the reference does not check)
+std::string mxn_grid_error(int64_t rows_m, int64_t cols_n);
 
 }  // namespace trik_hsv
 #pragma GCC visibility pop

@@ -368,6 +368,41 @@ int launch_blob_meta_chroma(const BlobArgs& a, const ChromaTables* ct, const Ran
 // guide lines + a 3x3 mark per kept target (OSEQ:548-580), from BlobArgs.top
 int launch_blob_overlay(const PreviewArgs& a, const int32_t* top, hipStream_t s);
 
+// ov7670 MxN colour-grid sensor of N frames (trik_hsv_mxn.hip).
+// rows_m is the reference's InArgs widthM (cell rows), cols_n its heightN
+// (cell columns): MSEQ:585-588 crosses the names.
+struct MxnArgs {
+  const uint8_t* frames;
+  int64_t frame_stride;
+  int32_t n_frames, width, height, line_length;
+  int32_t rows_m, cols_n;
+  int32_t row_step, col_step;  // height / rows_m, width / cols_n (truncated; 0: empty cells)
+  int32_t aligned4;            // frames, stride and line length 4-byte aligned
+  const uint32_t* table;       // device copy of mxn_color_table()
+  int32_t* colors;             // [n][rows_m * cols_n]
+  uint16_t* bins;              // optional [n][rows_m * cols_n]: h << 4 | s << 2 | v
+};
+struct MxnPreviewArgs {
+  const uint8_t* frames;
+  int64_t frame_stride;
+  int32_t n_frames, width, height, line_length;
+  int32_t rows_m, cols_n, row_step, col_step;
+  const int32_t* colors;  // [n][rows_m * cols_n]
+  int32_t out_w, out_h, out_ll;
+  uint8_t* previews;
+  int64_t preview_stride;
+  const uint32_t* wi2wo;    // [width]  (preview_maps)
+  const uint32_t* hi2ho;    // [height]
+  const int32_t* last_row;  // [out_h]
+  const int32_t* last_col;  // [out_w]
+};
+int launch_mxn(const MxnArgs& a, hipStream_t s);
+int launch_mxn_preview(const MxnPreviewArgs& a, hipStream_t s);
+// The sensor's colour table (trik_hsv_tables.cpp, host): entry h << 4 | s << 2
+// | v is HSVtoRGB(8 h, 64 s, 64 v) of MSEQ:480-517, built once.
+constexpr int kMxnColors = 32 * 4 * 4;
+const uint32_t* mxn_color_table();
+
 // Host side of the preview geometry (trik_hsv_tables.cpp): the reference's
 // scale maps and their inverses, packed as
 //   wi2wo[width], hi2ho[height], last_row[out_h], last_col[out_w]  (32-bit each).

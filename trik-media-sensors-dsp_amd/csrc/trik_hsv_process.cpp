@@ -144,6 +144,27 @@ int32_t process_blob(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
   return 0;
 }
 
+// BallDetector<YUV422P>::run of the MxN sensor, MSEQ:576-621.  outColor past
+// widthM * heightN is left as the caller had it.
+int32_t process_mxn(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewOut& pv, int rows_m, int cols_n,
+                    TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg& oa) {
+  const int cells = rows_m * cols_n;
+  if (!h->d_mxn_colors) HIP_TRY(hipMalloc(&h->d_mxn_colors, sizeof(int32_t) * 100));
+  int32_t r = mxn_core(h, b, rows_m, cols_n, h->d_mxn_colors, nullptr, h->stream);
+  if (r) return r;
+  if (pv.bytes) {  // preview: every pixel, then the cells' squares
+    r = mxn_preview_core(h, b, rows_m, cols_n, h->d_mxn_colors, h->out_w, h->out_h, h->out_ll, h->d_preview,
+                         (int64_t)pv.bytes, h->stream);
+    if (r) return r;
+  }
+  int32_t colors[100];
+  if (pv.bytes) HIP_TRY(hipMemcpyAsync(pv.ptr, h->d_preview, pv.bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(colors, h->d_mxn_colors, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  memcpy(oa.outColor, colors, sizeof(int32_t) * cells);
+  return 0;
+}
+
 // The algorithm's run on a checked frame: the targets cleared, then a frame
 // of non-zero size staged and taken through the handle's sensor.
 int32_t run_sensor(TrikCvHandle* h, const void* frame, const PreviewOut& pv, const TRIK_VIDTRANSCODE_CV_InArgs* in_args,
@@ -151,6 +172,22 @@ int32_t run_sensor(TrikCvHandle* h, const void* frame, const PreviewOut& pv, con
   TRIK_VIDTRANSCODE_CV_OutArgsAlg& oa = out_args->alg;
   auto* ia7 = reinterpret_cast<const TRIK_VIDTRANSCODE_CV_OV7670_InArgs*>(in_args);
   auto* oa7 = reinterpret_cast<TRIK_VIDTRANSCODE_CV_OV7670_OutArgs*>(out_args);
+  if (h->algo == kAlgoMxn) {
+    // The grid is checked here, the reference does not (0 divides by zero,
+    // more than 100 cells overrun outColor): an invalid one fails the run.
+    const auto& im = reinterpret_cast<const TRIK_VIDTRANSCODE_CV_MXN_InArgs*>(in_args)->alg;
+    auto& om = reinterpret_cast<TRIK_VIDTRANSCODE_CV_MXN_OutArgs*>(out_args)->alg;
+    const std::string e = mxn_grid_error(im.widthM, im.heightN);
+    if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+    if (h->in_w <= 0 || h->in_h <= 0) {  // every cell is empty: bin (0, 0, 0)
+      for (int k = 0; k < im.widthM * im.heightN; ++k) om.outColor[k] = (int32_t)mxn_color_table()[0];
+      return 0;
+    }
+    DeviceGuard dg(h->device);
+    TrikHsvFrameBatch b;
+    const int32_t r = stage_frame(h, frame, pv.bytes, b);
+    return r ? r : process_mxn(h, b, pv, im.widthM, im.heightN, om);
+  }
   if (h->algo == kAlgoBlob)
     memset(oa7->alg.target, 0, sizeof oa7->alg.target);  // OSEQ:563
   else {
@@ -179,11 +216,14 @@ extern "C" int32_t TRIK_VIDTRANSCODE_CV_process(TRIK_VIDTRANSCODE_CV_Handle h,
   if (!h || !in_bufs || !out_bufs || !in_args || !out_args)
     return fail(TRIK_IVIDTRANSCODE_EFAIL, "NULL argument");
   std::lock_guard<std::mutex> lock(h->mu);
-  const bool blob = h->algo == kAlgoBlob;  // the ov7670 object sensor's own InArgs / OutArgs
-  const int32_t in_want = blob ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_InArgs)
-                               : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_InArgs);
-  const int32_t out_want = blob ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_OutArgs)
-                                : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OutArgs);
+  // the ov7670 object sensor and the MxN sensor have their own InArgs / OutArgs
+  const bool blob = h->algo == kAlgoBlob, mxn = h->algo == kAlgoMxn;
+  const int32_t in_want = blob  ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_InArgs)
+                          : mxn ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_MXN_InArgs)
+                                : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_InArgs);
+  const int32_t out_want = blob  ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_OutArgs)
+                           : mxn ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_MXN_OutArgs)
+                                 : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OutArgs);
   if (in_args->base.size != in_want ||  // WFXNS:192-197
       out_args->base.size != out_want) {
     set_bit(out_args->base.extendedError, TRIK_XDM_UNSUPPORTEDPARAM_BIT);

@@ -361,6 +361,68 @@ int32_t trik_hsv::blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
   return note_uses(h, set, false, s, &h->blob_users);
 }
 
+std::string trik_hsv::mxn_grid_error(int64_t rows_m, int64_t cols_n) {
+  if (rows_m < 1 || cols_n < 1 || rows_m * cols_n > 100)
+    return "the MxN sensor takes widthM >= 1, heightN >= 1 and widthM * heightN <= 100";
+  return "";
+}
+
+// GetImgColor2 of every cell (MSEQ:604-618); the steps are truncating
+// divisions (MSEQ:587-588), pixels right of or below the last cell count nowhere
+int32_t trik_hsv::mxn_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int cols_n, int32_t* colors,
+                           uint16_t* bins, hipStream_t s) {
+  if (!h->d_mxn_table) {  // once per handle; the host table is static
+    uint32_t* t = nullptr;
+    HIP_TRY(hipMalloc(&t, sizeof(uint32_t) * kMxnColors));
+    hipError_t e = hipMemcpyAsync(t, mxn_color_table(), sizeof(uint32_t) * kMxnColors, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // later calls may run on other streams
+    if (e != hipSuccess) {
+      (void)hipFree(t);
+      return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("MxN colour table upload: ") + hipGetErrorString(e));
+    }
+    h->d_mxn_table = t;
+  }
+  MxnArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  a.rows_m = rows_m; a.cols_n = cols_n;
+  a.row_step = b.height / rows_m;
+  a.col_step = b.width / cols_n;
+  a.aligned4 = aligned4(b);
+  a.table = h->d_mxn_table;
+  a.colors = colors;
+  a.bins = bins;
+  HIP_TRY(launch_mxn(a, s));
+  return 0;
+}
+
+int32_t trik_hsv::mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int cols_n,
+                                   const int32_t* colors, int ow, int oh, int oll, uint8_t* previews,
+                                   int64_t stride, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+  if (rc) return rc;
+  MxnPreviewArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  a.rows_m = rows_m; a.cols_n = cols_n;
+  a.row_step = b.height / rows_m;
+  a.col_step = b.width / cols_n;
+  a.colors = colors;
+  a.out_w = ow; a.out_h = oh; a.out_ll = oll;
+  a.previews = previews;
+  a.preview_stride = stride;
+  a.wi2wo = h->d_maps;
+  a.hi2ho = a.wi2wo + b.width;
+  a.last_row = reinterpret_cast<const int32_t*>(a.hi2ho + b.height);
+  a.last_col = a.last_row + oh;
+  HIP_TRY(launch_mxn_preview(a, s));
+  return note_uses(h, nullptr, true, s);
+}
+
 int32_t trik_hsv::blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta,
                                     const int32_t* top, int ow, int oh, int oll, uint8_t* previews, int64_t stride,
                                     hipStream_t s) {

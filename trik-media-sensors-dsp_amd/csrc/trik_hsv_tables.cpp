@@ -145,6 +145,46 @@ void preview_maps(int width, int height, int out_w, int out_h, uint32_t* maps, i
     if (i >= col_lo && i <= col_hi && wi2wo[i] < (uint32_t)out_w) last_col[wi2wo[i]] = i;
 }
 
+// HSVtoRGB of the MxN sensor (MSEQ:480-517): h, s, v are float divisions
+// widened to double, s is forced to 0 or 1, f, p, q, t are doubles, and the
+// channels are truncated.  Contraction is off: fusing 1 - f * s into an FMA
+// changes low bits, and with them a truncated channel.
+static uint32_t mxn_hsv_to_rgb(int H, int S, int V) {
+#pragma clang fp contract(off)
+  double r = 0, g = 0, b = 0;
+  const double h = (float)H / 255.0f;
+  double s = (float)S / 255.0f;
+  double v = (float)V / 255.0f;
+  v = v < 0.2 ? 0 : v;
+  s = s < 0.2 ? 0 : 1;
+  const int i = (int)(h * 6);
+  const double f = h * 6 - i;
+  const double p = v * (1 - s);
+  const double q = v * (1 - f * s);
+  const double t = v * (1 - (1 - f) * s);
+  switch (i % 6) {
+    case 0: r = v; g = t; b = p; break;
+    case 1: r = q; g = v; b = p; break;
+    case 2: r = p; g = v; b = t; break;
+    case 3: r = p; g = q; b = v; break;
+    case 4: r = t; g = p; b = v; break;
+    case 5: r = v; g = p; b = q; break;
+  }
+  const int ri = (int)(r * 255), gi = (int)(g * 255), bi = (int)(b * 255);
+  return (uint32_t)((ri << 16) + (gi << 8) + bi);
+}
+
+const uint32_t* mxn_color_table() {
+  struct Table {
+    uint32_t c[kMxnColors];
+    Table() {
+      for (int i = 0; i < kMxnColors; ++i) c[i] = mxn_hsv_to_rgb(8 * (i >> 4), 64 * ((i >> 2) & 3), 64 * (i & 3));
+    }
+  };
+  static const Table t;  // built once, on first use
+  return t.c;
+}
+
 void auto_range_zone(int width, int height, int32_t& c_lo, int32_t& c_hi, int32_t& r_lo, int32_t& r_hi) {
   // HsvRangeDetector::initImg (cv_hsv_range_detector.hpp:88-108), zone scale 6
   // (WSEQ:32): uint16_t fields, so differences wrap modulo 2^16.

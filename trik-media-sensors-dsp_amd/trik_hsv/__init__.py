@@ -283,6 +283,41 @@ class Detector(_HotKernel):
             raise TrikHsvError(rc, "trik_hsv_blob_preview")
         return previews
 
+    def mxn_batch(self, frames, width, height, line_length, m, n, *, n_frames=None, frame_stride=None,
+                  bins=False, stream=None):
+        """The ov7670 MxN colour-grid sensor over N frames (MSEQ:576-621): m
+        cell rows (InArgs widthM) x n cell columns (heightN).  Returns colors
+        int32 [N, m * n] (outColor of each frame), or (colors, bins int16
+        [N, m * n] = h << 4 | s << 2 | v of the winning bins) when asked."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
+        cells = max(int(m) * int(n), 0)
+        colors = torch.empty((b.n_frames, cells), dtype=torch.int32, device=frames.device)
+        bn = torch.empty((b.n_frames, cells), dtype=torch.int16, device=frames.device) if bins else None
+        rc = _lib.trik_hsv_mxn_batch(self._h, C.byref(b), int(m), int(n), C.c_void_p(colors.data_ptr()),
+                                     C.c_void_p(bn.data_ptr()) if bins else None, _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_mxn_batch")
+        return (colors, bn) if bins else colors
+
+    def mxn_preview(self, frames, width, height, line_length, m, n, colors, *, out_width=None,
+                    out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
+        """MxN previews (uint8 [N, out_height, out_line_length]) from mxn_batch's colors."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
+        ow = width // 2 if out_width is None else out_width
+        oh = height // 2 if out_height is None else out_height
+        oll = 2 * ow if out_line_length is None else out_line_length
+        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        rc = _lib.trik_hsv_mxn_preview(self._h, C.byref(b), int(m), int(n), C.c_void_p(colors.data_ptr()),
+                                       ow, oh, oll, C.c_void_p(previews.data_ptr()), oh * oll,
+                                       _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_mxn_preview")
+        return previews
+
     def line_preview(self, frames, width, height, line_length, val_from, val_to, sums, *,
                      out_width=None, out_height=None, out_line_length=None, n_frames=None,
                      frame_stride=None, stream=None):
@@ -321,6 +356,12 @@ def line_batch(frames, width, height, line_length, val_from, val_to, *, band=Non
     if rc:
         raise TrikHsvError(rc, "trik_hsv_line_batch")
     return sums, targets
+
+
+def mxn_color(h: int, s: int, v: int) -> int:
+    """The MxN sensor's 0x00RRGGBB colour of histogram bin (h 0..31, s 0..3,
+    v 0..3): trik_hsv_mxn_color, host code."""
+    return int(_lib.trik_hsv_mxn_color(int(h), int(s), int(v)))
 
 
 def batch_auto_range(frames, width, height, line_length, layout, *, n_frames=None,
@@ -649,3 +690,34 @@ class BlobSensor(ObjectSensor):
         oa.base.size = C.sizeof(_abi.OV7670OutArgs)
         rc = _lib.TRIK_VIDTRANSCODE_CV_process(self._h, C.byref(ib), C.byref(ob), C.byref(ia), C.byref(oa))
         return rc, oa
+
+
+class MxnSensor(ObjectSensor):
+    """The ov7670 MxN colour-grid sensor's codec instance (trik/ov7670/mxn_sensor:
+    BallDetector<YUV422P, RGB565X> behind the ov7670 object sensor's glue): its
+    own InArgs (widthM = cell rows, heightN = cell columns) and OutArgs
+    (outColor[100])."""
+
+    _create = "TRIK_VIDTRANSCODE_CV_create_mxn"
+
+    def __init__(self, params: _abi.Params | None = None):
+        super().__init__(params)
+        if params is None:
+            self.params = _default_params(1, fmt_in=FORMAT_YUV422P)
+
+    def process(self, frame, m, n, out_buffer=None, num_bytes=None, input_id=0, out_args=None):
+        """One host frame -> (rc, MxnOutArgs, colors): colors is the list of
+        the m * n cell colours (None unless rc is EOK).  `out_args`: a
+        prepared MxnOutArgs to fill instead of a fresh one."""
+        fr, ib, ob, keep = self._bufs(frame, out_buffer, num_bytes)
+        ia = _abi.MxnInArgs()
+        ia.base.size = C.sizeof(_abi.MxnInArgs)
+        ia.base.numBytes = fr.size if num_bytes is None else num_bytes
+        ia.base.inputID = input_id
+        ia.alg = _abi.MxnInArgsAlg(int(m), int(n))
+        oa = out_args if out_args is not None else _abi.MxnOutArgs()
+        if out_args is None:
+            oa.base.size = C.sizeof(_abi.MxnOutArgs)
+        rc = _lib.TRIK_VIDTRANSCODE_CV_process(self._h, C.byref(ib), C.byref(ob), C.byref(ia), C.byref(oa))
+        colors = list(oa.alg.outColor[: int(m) * int(n)]) if rc == IVIDTRANSCODE_EOK else None
+        return rc, oa, colors

@@ -107,6 +107,17 @@ class OV7670OutArgsAlg(C.Structure):
                 ("detectValTolerance", u16)]
 
 
+class MxnInArgsAlg(C.Structure):
+    """TRIK_VIDTRANSCODE_CV_MXN_InArgsAlg (ov7670 mxn_sensor trik_vidtranscode_cv.h:49-52):
+    widthM = cell rows, heightN = cell columns (the reference crosses the names)."""
+    _fields_ = [("widthM", i32), ("heightN", i32)]
+
+
+class MxnOutArgsAlg(C.Structure):
+    """TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg (ov7670 mxn_sensor trik_vidtranscode_cv.h:60-62)."""
+    _fields_ = [("outColor", i32 * 100)]
+
+
 class SingleBufDesc(C.Structure):
     _fields_ = [("buf", C.c_void_p), ("bufSize", i32), ("accessMask", i32)]
 
@@ -140,6 +151,14 @@ class OV7670OutArgs(C.Structure):
     _fields_ = [("base", IVidtranscodeOutArgs), ("alg", OV7670OutArgsAlg)]
 
 
+class MxnInArgs(C.Structure):
+    _fields_ = [("base", IVidtranscodeInArgs), ("alg", MxnInArgsAlg)]
+
+
+class MxnOutArgs(C.Structure):
+    _fields_ = [("base", IVidtranscodeOutArgs), ("alg", MxnOutArgsAlg)]
+
+
 class AlgBufInfo(C.Structure):
     _fields_ = [("minNumInBufs", i32), ("minNumOutBufs", i32),
                 ("minInBufSize", i32 * MAX_IO_BUFFERS), ("minOutBufSize", i32 * MAX_IO_BUFFERS)]
@@ -169,9 +188,11 @@ PROTOTYPES = {
     "TRIK_VIDTRANSCODE_CV_create_line": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_create_ov7670": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_create_webcam_line": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
+    "TRIK_VIDTRANSCODE_CV_create_mxn": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_delete": ([C.c_void_p], i32),
-    # InArgs / OutArgs by pointer: the webcam structs, or the OV7670 ones for
-    # a create_ov7670 handle (their base.size fields say which)
+    # InArgs / OutArgs by pointer: the webcam structs, the OV7670 ones for a
+    # create_ov7670 handle or the MXN ones for a create_mxn handle (their
+    # base.size fields say which)
     "TRIK_VIDTRANSCODE_CV_process": ([C.c_void_p, C.POINTER(BufDesc1), C.POINTER(BufDesc),
                                       C.c_void_p, C.c_void_p], i32),
     "TRIK_VIDTRANSCODE_CV_control": ([C.c_void_p, i32, C.POINTER(DynamicParams),
@@ -199,6 +220,11 @@ PROTOTYPES = {
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
     "trik_hsv_blob_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, C.c_void_p, i32, i32, i32,
                                C.c_void_p, C.c_int64, C.c_void_p], i32),
+    "trik_hsv_mxn_batch": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, C.c_void_p,
+                            C.c_void_p], i32),
+    "trik_hsv_mxn_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,
+                              C.c_void_p, C.c_int64, C.c_void_p], i32),
+    "trik_hsv_mxn_color": ([i32, i32, i32], C.c_uint32),
     "trik_hsv_synth": ([C.POINTER(FrameBatch), i32, i32, u64, C.c_void_p], i32),
     "trik_hsv_set_hot_kernel": ([C.c_void_p, i32], i32),
     "trik_hsv_last_hot_kernel": ([C.c_void_p], i32),

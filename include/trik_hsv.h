@@ -218,6 +218,20 @@ typedef struct TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg {
   int32_t outColor[100];
 } TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg;
 
+/* The ov7670 JPEG encoder's InArgsAlg and OutArgsAlg (JPUB = trik/ov7670/
+ * jpeg_encoder/trik_vidtranscode_cv.h:49-67), field names as the reference's.
+ * XDAS_Bool is a 32-bit int.  jpgImageQuality is clamped to 1..100 by the
+ * encoder (0 encodes as 1, 101..255 as 100); size is the stream's length in
+ * bytes. */
+typedef struct TRIK_VIDTRANSCODE_CV_JPEG_InArgsAlg {
+  uint8_t jpgImageQuality;
+  int32_t ifBlackAndWhite; /* non-zero: the luma plane alone, one component */
+} TRIK_VIDTRANSCODE_CV_JPEG_InArgsAlg;
+
+typedef struct TRIK_VIDTRANSCODE_CV_JPEG_OutArgsAlg {
+  uint32_t size;
+} TRIK_VIDTRANSCODE_CV_JPEG_OutArgsAlg;
+
 /* XDM1_SingleBufDesc */
 typedef struct TRIK_XDM1_SingleBufDesc {
   int8_t* buf;
@@ -275,6 +289,16 @@ typedef struct TRIK_VIDTRANSCODE_CV_MXN_OutArgs { /* MPUB:64-67 */
   TRIK_IVIDTRANSCODE_OutArgs base;
   TRIK_VIDTRANSCODE_CV_MXN_OutArgsAlg alg;
 } TRIK_VIDTRANSCODE_CV_MXN_OutArgs;
+
+typedef struct TRIK_VIDTRANSCODE_CV_JPEG_InArgs { /* JPUB:54-57 */
+  TRIK_IVIDTRANSCODE_InArgs base;
+  TRIK_VIDTRANSCODE_CV_JPEG_InArgsAlg alg;
+} TRIK_VIDTRANSCODE_CV_JPEG_InArgs;
+
+typedef struct TRIK_VIDTRANSCODE_CV_JPEG_OutArgs { /* JPUB:64-67 */
+  TRIK_IVIDTRANSCODE_OutArgs base;
+  TRIK_VIDTRANSCODE_CV_JPEG_OutArgsAlg alg;
+} TRIK_VIDTRANSCODE_CV_JPEG_OutArgs;
 
 /* XDM1_AlgBufInfo subset filled by GETSTATUS/GETBUFINFO (WFXNS:287-297) */
 typedef struct TRIK_XDM1_AlgBufInfo {
@@ -366,6 +390,37 @@ int32_t TRIK_VIDTRANSCODE_CV_create_ov7670(const TRIK_VIDTRANSCODE_CV_Params* pa
 int32_t TRIK_VIDTRANSCODE_CV_create_mxn(const TRIK_VIDTRANSCODE_CV_Params* params,
                                         TRIK_VIDTRANSCODE_CV_Handle* out_handle);
 
+/* The quartet for the ov7670 JPEG encoder's codec (trik/ov7670/jpeg_encoder:
+ * JPGEncoderWrapper<YUV422P, RGB565X> of include/internal/
+ * cv_jpeg_encoder_wrapper_seqpass.hpp -- JWRAP -- over JPGEncoder of
+ * jpeg_encoder_reference.hpp -- JENC -- behind the ov7670 object sensor's
+ * glue).  params == NULL takes that glue's defaults (YUV422P in, "RGB565X"
+ * out).  process() then takes TRIK_VIDTRANSCODE_CV_JPEG_InArgs and
+ * TRIK_VIDTRANSCODE_CV_JPEG_OutArgs (size fields checked).  The output
+ * buffer, declared RGB565X, receives a baseline JFIF stream: SOI, APP0, DQT,
+ * SOF0, DHT, SOS (607 bytes in colour, 324 in black and white), the
+ * entropy-coded 8x8 blocks in raster order (Y, U, V per block; colour is
+ * declared 4:4:4 with each chroma sample repeated for two pixels), fill bits
+ * and EOI -- the reference's bytes, its truncating fp64 AAN transform, its
+ * 8 fill bits on an aligned end and its unwritten undefined Huffman symbols
+ * included.  OutArgs.alg.size is the stream's length.  process() keeps the
+ * wrapper's two buffer checks (the input holds the image, the output buffer
+ * holds outputHeight * outputLineLength bytes: JWRAP:55-58).  Without an
+ * output stream the size alone is reported; with a zero width or height
+ * nothing is encoded and size is left untouched (JWRAP:67).  The divergences:
+ *  - a height that is no multiple of 8: the reference's block walk reads the
+ *    chroma plane as luma and past the buffer as chroma; here process()
+ *    returns IVIDTRANSCODE_EFAIL with nothing written;
+ *  - a stream longer than the output buffer: the reference writes on past
+ *    it; here process() returns IVIDTRANSCODE_EFAIL with none of the stream
+ *    written (the buffer keeps the shell's zero fill);
+ *  - a width or height above 65535 is rejected (SOF0 holds 16 bits; setup
+ *    already rejects sides above 32767);
+ *  - both planes are checked against the input buffer, as for every ov7670
+ *    codec here. */
+int32_t TRIK_VIDTRANSCODE_CV_create_jpeg(const TRIK_VIDTRANSCODE_CV_Params* params,
+                                         TRIK_VIDTRANSCODE_CV_Handle* out_handle);
+
 /* Replaces TRIK_VIDTRANSCODE_CV_free (WFXNS:114-136). */
 int32_t TRIK_VIDTRANSCODE_CV_delete(TRIK_VIDTRANSCODE_CV_Handle handle);
 
@@ -446,16 +501,17 @@ typedef struct TRIK_IVIDTRANSCODE_Fxns {
 
 /* The webcam object sensor's tables (WFXNS:36-66); IALG is the same table
  * as FXNS.ialg (the reference aliases the two symbols on TI toolchains and
- * duplicates them elsewhere, as here).  The other four codecs of this library
+ * duplicates them elsewhere, as here).  The other five codecs of this library
  * (one DSP server each in the reference, all named TRIK_VIDTRANSCODE_CV_FXNS
  * there): the ov7670 object sensor, the ov7670 line sensor, the webcam line
- * sensor and the ov7670 MxN sensor. */
+ * sensor, the ov7670 MxN sensor and the ov7670 JPEG encoder. */
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_FXNS;
 extern TRIK_IALG_Fxns TRIK_VIDTRANSCODE_CV_IALG;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_OV7670_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_LINE_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_MXN_FXNS;
+extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_JPEG_FXNS;
 
 /* The webcam object sensor's IALG functions (WFXNS:85-166), also reachable
  * through the tables.  alloc asks for one persistent external record (the
@@ -688,6 +744,36 @@ int32_t trik_hsv_mxn_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFr
  * 0..3): HSVtoRGB(8 h_bin, 64 s_bin, 64 v_bin) of MSEQ:480-517 as 0x00RRGGBB
  * (0 for a bin out of range).  Host code: a table built once, no GPU call. */
 uint32_t trik_hsv_mxn_color(int32_t h_bin, int32_t s_bin, int32_t v_bin);
+
+/* The ov7670 JPEG encoder for N ov7670 frames: frame i's
+ * stream (see TRIK_VIDTRANSCODE_CV_create_jpeg) goes to out_dev + i *
+ * out_stride.
+ *   sizes_dev  [N] uint32: always the full length of each stream, like
+ *              snprintf; a frame whose length exceeds out_capacity has
+ *              nothing written to its slot;
+ *   out_dev    may be NULL for a sizes-only call (else out_stride >=
+ *              out_capacity when N > 1);
+ *   coeffs_dev optional [N][blocks][components][64] int16: the quantised
+ *              coefficients in zigzag order, blocks in raster order,
+ *              components Y, U, V (Y alone in black and white) -- a
+ *              verification output.
+ * quality is clamped to 1..100.  The layout must be ov7670; line_length is
+ * honoured (the reference uses width as the stride).  height % 8 != 0 and
+ * sides above 65535 fail with trik_hsv_last_error() and write nothing; a
+ * zero width or height gives sizes of 0.  Stream-ordered, no host
+ * synchronisation; scratch lives in the handle and is bounded independently
+ * of N (batches go through it in chunks of frames). */
+int32_t trik_hsv_jpeg_batch(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch, int32_t quality,
+                            int32_t black_and_white, uint8_t* out_dev, int64_t out_stride, int64_t out_capacity,
+                            uint32_t* sizes_dev, int16_t* coeffs_dev, void* hip_stream);
+
+/* The encoder's header for a width x height frame: SOI, APP0 (JFIF 1.1), DQT
+ * (the Annex K.1 tables scaled by quality, zigzag order), SOF0, DHT (the four
+ * Annex K.3 tables), SOS (JENC:517-647).  Returns its length (607 in colour,
+ * 324 in black and white) and writes it when out != NULL and capacity is
+ * large enough; 0 for a side outside 0..65535.  Host code, no GPU call. */
+int32_t trik_hsv_jpeg_header(int32_t quality, int32_t black_and_white, int32_t width, int32_t height, uint8_t* out,
+                             int32_t capacity);
 
 /* Fill batch->frames (device, writable) with synthetic frames; frame i of the
  * batch is global frame first_frame + i.  kind 0 = uniform random bytes,

@@ -14,6 +14,10 @@
   mxn         trik_hsv_mxn_batch: the MxN colour-grid sensor over the same
               ov7670 frames at 3x3 and 10x10 cells, scene and uniform random
               bytes; algorithmic bytes = both planes once, as the line row.
+  jpeg        trik_hsv_jpeg_batch: the JPEG encoder over the same ov7670 frames,
+              scene and uniform random bytes, quality 50 and 100, colour and
+              black-and-white; algorithmic bytes = both planes once plus the
+              stream bytes written.
   process     one host frame through the XDAIS quartet (H2D + kernels + D2H,
               PCIe-inclusive latency per frame), with preview and auto range.
 
@@ -128,6 +132,29 @@ def main():
                                              "achieved_GBs": round(lf * lfb / (ms / 1e3) / 1e9, 1),
                                              "hbm_frac": round(lf * lfb / (ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                                              "over_line": round(ms / ln_ms, 2)}
+    # the JPEG encoder over the same frames: scene, then uniform random bytes;
+    # each stream written whole (the capacity is the batch's longest stream)
+    out["jpeg"] = {"frames": lf,
+                   "note": "jpeg_block / scan / zero / emit / count / sizes / stuff kernels per chunk of frames; "
+                           "bytes_algorithmic = both planes + the streams written"}
+    jbuf = None
+    for kind, name in ((1, "scene"), (0, "uniform")):
+        trik_hsv.synth(ldev, W, H, W, trik_hsv.LAYOUT_OV7670, kind, 0x7A1C)
+        for q in (100, 50):
+            for bw in (False, True):
+                _, sizes = det.jpeg_batch(ldev, W, H, W, q, bw, sizes_only=True)
+                cap, written = int(sizes.max()), int(sizes.sum(dtype=torch.int64))
+                if jbuf is None or jbuf.numel() < lf * cap:
+                    jbuf = None
+                    jbuf = torch.empty(lf * cap, dtype=torch.uint8, device="cuda")
+                view = jbuf[: lf * cap].view(lf, cap)
+                ms = timed(lambda: det.jpeg_batch(ldev, W, H, W, q, bw, capacity=cap, out=view), stream, args.iters)
+                nbytes = lf * lfb + written
+                out["jpeg"][f"{name}_q{q}_{'bw' if bw else 'colour'}"] = {
+                    "ms": round(ms, 4), "Mframes_per_s": round(lf / ms / 1e3, 4), "stream_bytes_per_frame": written // lf,
+                    "bytes_algorithmic": nbytes, "achieved_GBs": round(nbytes / (ms / 1e3) / 1e9, 1),
+                    "hbm_frac": round(nbytes / (ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4), "over_line": round(ms / ln_ms, 2)}
+    del jbuf
     del ldev
 
     s = trik_hsv.ObjectSensor()

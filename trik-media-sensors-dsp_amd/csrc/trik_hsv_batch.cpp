@@ -1,6 +1,8 @@
 // trik_hsv_batch.cpp -- Layer 2 of the C ABI: the batched device API
 // (trik_hsv_*), each entry point its argument checks and then the shared
 // enqueue path (run_sums, or the sensor's core in trik_hsv_sensors.cpp).
+#include <string.h>
+
 #include "trik_hsv_handle.h"
 
 using namespace trik_hsv;
@@ -323,6 +325,45 @@ extern "C" uint32_t trik_hsv_mxn_color(int32_t h_bin, int32_t s_bin, int32_t v_b
     return 0;
   }
   return mxn_color_table()[(h_bin << 4) | (s_bin << 2) | v_bin];
+}
+
+extern "C" int32_t trik_hsv_jpeg_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, int32_t quality,
+                                       int32_t black_and_white, uint8_t* out, int64_t out_stride,
+                                       int64_t out_capacity, uint32_t* sizes, int16_t* coeffs, void* stream) {
+  int32_t r = check_handle_batch(h, b);
+  if (!r) r = check_ov7670(b, "JPEG");
+  if (r) return r;
+  const std::string e = jpeg_geometry_error(b->width, b->height);
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  if (out_capacity < 0 || (out && b->n_frames > 1 && out_stride < out_capacity))
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "jpeg_batch: need out_capacity >= 0 and out_stride >= out_capacity");
+  if (b->n_frames > 0 && !sizes) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sizes is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0) return 0;
+  r = check_device(h, b, sizes);
+  if (r) return r;
+  std::string de = device_buffer_error(out, h->device, "out");
+  if (de.empty()) de = device_buffer_error(coeffs, h->device, "coeffs");
+  if (!de.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, de);
+  if (b->width == 0 || b->height == 0) {  // the reference encodes nothing (JWRAP:67): empty streams
+    HIP_TRY(hipMemsetAsync(sizes, 0, sizeof(uint32_t) * (size_t)b->n_frames, s));
+    return 0;
+  }
+  return jpeg_core(h, *b, quality, black_and_white != 0, out, out_stride, out_capacity, sizes, coeffs, s);
+}
+
+extern "C" int32_t trik_hsv_jpeg_header(int32_t quality, int32_t black_and_white, int32_t width, int32_t height,
+                                        uint8_t* out, int32_t capacity) {
+  if (width < 0 || height < 0 || width > 65535 || height > 65535) {
+    fail(TRIK_IVIDTRANSCODE_EFAIL, "jpeg_header: need 0 <= width, height <= 65535 (SOF0 holds 16 bits)");
+    return 0;
+  }
+  JpegHeader hd;
+  jpeg_header(quality, black_and_white != 0, width, height, hd);
+  if (out && capacity >= hd.size) memcpy(out, hd.bytes, (size_t)hd.size);
+  return hd.size;
 }
 
 extern "C" int32_t trik_hsv_synth(const TrikHsvFrameBatch* b, int32_t first_frame, int32_t kind,

@@ -102,6 +102,8 @@ void free_resources(TrikCvHandle* h) {
   h->maps_users.release();
   h->blob_users.wait_all();
   h->blob_users.release();
+  h->jpeg_users.wait_all();
+  h->jpeg_users.release();
   h->fused_users.wait_all();
   h->fused_users.release();
   h->marks.release();
@@ -120,6 +122,9 @@ void free_resources(TrikCvHandle* h) {
   (void)hipFree(h->d_blob_targets);
   (void)hipFree(h->d_mxn_table);
   (void)hipFree(h->d_mxn_colors);
+  (void)hipFree(h->d_jpeg_huff);
+  (void)hipFree(h->d_jpeg_scratch);
+  (void)hipFree(h->d_jpeg_size);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   h->stream = nullptr;
   h->d_frame = nullptr; h->d_frame_cap = 0;
@@ -134,6 +139,8 @@ void free_resources(TrikCvHandle* h) {
   h->d_blob_top = nullptr; h->d_blob_top_cap = 0;
   h->d_blob_targets = nullptr; h->d_blob_targets_cap = 0;
   h->d_mxn_table = nullptr; h->d_mxn_colors = nullptr;
+  h->d_jpeg_huff = nullptr; h->d_jpeg_size = nullptr;
+  h->d_jpeg_scratch = nullptr; h->d_jpeg_scratch_cap = 0;
   h->d_wg_part = nullptr; h->d_wg_cnt = nullptr;
   h->d_frame_acc = nullptr; h->frame_acc_cap = 0;
   h->d_tail_sink = nullptr;
@@ -214,7 +221,8 @@ int32_t setup_dynamic(TrikCvHandle* h, const TRIK_VIDTRANSCODE_CV_DynamicParams*
 // Layer 1: XDAIS-shaped quartet (process: trik_hsv_process.cpp)
 // ---------------------------------------------------------------------------
 extern "C" TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_FXNS, TRIK_VIDTRANSCODE_CV_OV7670_FXNS,
-    TRIK_VIDTRANSCODE_CV_LINE_FXNS, TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS, TRIK_VIDTRANSCODE_CV_MXN_FXNS;
+    TRIK_VIDTRANSCODE_CV_LINE_FXNS, TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS, TRIK_VIDTRANSCODE_CV_MXN_FXNS,
+    TRIK_VIDTRANSCODE_CV_JPEG_FXNS;
 
 static const TRIK_IALG_Fxns* table_of(int algo) {
   switch (algo) {
@@ -222,6 +230,7 @@ static const TRIK_IALG_Fxns* table_of(int algo) {
     case kAlgoBlob: return &TRIK_VIDTRANSCODE_CV_OV7670_FXNS.ialg;
     case kAlgoWLine: return &TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS.ialg;
     case kAlgoMxn: return &TRIK_VIDTRANSCODE_CV_MXN_FXNS.ialg;
+    case kAlgoJpeg: return &TRIK_VIDTRANSCODE_CV_JPEG_FXNS.ialg;
     default: return &TRIK_VIDTRANSCODE_CV_FXNS.ialg;
   }
 }
@@ -247,7 +256,7 @@ static int32_t init_handle(TrikCvHandle* h, int algo, const TRIK_VIDTRANSCODE_CV
   h->algo = algo;
   // (the webcam line sensor's glue has the webcam object sensor's Params)
   h->params = params ? *params
-                     : default_params(algo == kAlgoLine || algo == kAlgoBlob || algo == kAlgoMxn
+                     : default_params(algo == kAlgoLine || algo == kAlgoBlob || algo == kAlgoMxn || algo == kAlgoJpeg
                                           ? TRIK_VIDTRANSCODE_CV_VIDEO_FORMAT_YUV422P
                                           : TRIK_VIDTRANSCODE_CV_VIDEO_FORMAT_YUV422);  // WGLUE:188-191
   const int32_t rc = setup_dynamic(h, nullptr);      // WFXNS:158-163
@@ -293,6 +302,11 @@ extern "C" int32_t TRIK_VIDTRANSCODE_CV_create_ov7670(const TRIK_VIDTRANSCODE_CV
 extern "C" int32_t TRIK_VIDTRANSCODE_CV_create_mxn(const TRIK_VIDTRANSCODE_CV_Params* params,
                                                    TRIK_VIDTRANSCODE_CV_Handle* out_handle) {
   return create_handle(kAlgoMxn, params, out_handle);
+}
+
+extern "C" int32_t TRIK_VIDTRANSCODE_CV_create_jpeg(const TRIK_VIDTRANSCODE_CV_Params* params,
+                                                    TRIK_VIDTRANSCODE_CV_Handle* out_handle) {
+  return create_handle(kAlgoJpeg, params, out_handle);
 }
 
 extern "C" int32_t TRIK_VIDTRANSCODE_CV_delete(TRIK_VIDTRANSCODE_CV_Handle handle) {
@@ -424,6 +438,8 @@ TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS = {
     TRIK_IALGFXNS(TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS, ialg_init_as<kAlgoWLine>), xdais_process, xdais_control};
 TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_MXN_FXNS = {
     TRIK_IALGFXNS(TRIK_VIDTRANSCODE_CV_MXN_FXNS, ialg_init_as<kAlgoMxn>), xdais_process, xdais_control};
+TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_JPEG_FXNS = {
+    TRIK_IALGFXNS(TRIK_VIDTRANSCODE_CV_JPEG_FXNS, ialg_init_as<kAlgoJpeg>), xdais_process, xdais_control};
 }
 
 extern "C" int32_t TRIK_VIDTRANSCODE_CV_alloc(const TRIK_IALG_Params* params, TRIK_IALG_Fxns** parent_fxns,

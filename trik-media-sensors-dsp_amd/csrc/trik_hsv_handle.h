@@ -28,7 +28,10 @@
 // of trik/ov7670/mxn_sensor/include/internal/cv_ball_detector_seqpass.hpp --
 // MSEQ -- behind the ov7670 object sensor's glue: YUV422P input, a 320x240
 // default output).
-enum Algo { kAlgoBall = 0, kAlgoLine = 1, kAlgoBlob = 2, kAlgoWLine = 3, kAlgoMxn = 4 };
+// kAlgoJpeg: the ov7670 JPEG encoder (JPGEncoderWrapper<YUV422P, RGB565X> of
+// trik/ov7670/jpeg_encoder/include/internal/cv_jpeg_encoder_wrapper_seqpass.hpp
+// -- JWRAP -- over jpeg_encoder_reference.hpp -- JENC -- behind the same glue).
+enum Algo { kAlgoBall = 0, kAlgoLine = 1, kAlgoBlob = 2, kAlgoWLine = 3, kAlgoMxn = 4, kAlgoJpeg = 5 };
 
 // ---------------------------------------------------------------------------
 // Handle
@@ -294,7 +297,15 @@ struct TrikCvHandle {
   // read) and process()'s cell colours (used on the handle's stream only)
   uint32_t* d_mxn_table = nullptr;
   int32_t* d_mxn_colors = nullptr;
-  StreamMarks marks;      // the events the StreamUses lists point at (freed last)
+  // JPEG encoder: the Huffman tables' device copy (uploaded once, then only
+  // read), the pipeline's scratch for one chunk of frames (jpeg_core) and
+  // process()'s stream length (used on the handle's stream only)
+  trik_hsv::JpegHuffman* d_jpeg_huff = nullptr;
+  uint8_t* d_jpeg_scratch = nullptr;
+  size_t d_jpeg_scratch_cap = 0;
+  uint32_t* d_jpeg_size = nullptr;
+  StreamUses jpeg_users;  // calls that wrote the JPEG scratch
+  StreamMarks marks;     // the events the StreamUses lists point at (freed last)
 };
 
 // Everything below is internal to the library's own translation units.
@@ -404,6 +415,18 @@ int32_t mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m
 // "" when 1 <= rows_m, 1 <= cols_n and rows_m * cols_n <= 100 (OutArgs holds
 // 100 colours; the reference does not check)
 std::string mxn_grid_error(int64_t rows_m, int64_t cols_n);
+
+// the JPEG encoder: frame i's stream to out + i * out_stride when it fits
+// out_capacity (out NULL: sizes only), its length to sizes[i], the quantised
+// coefficients to coeffs when not NULL; the geometry validated by the caller
+// (jpeg_geometry_error).  Batches go through the handle's scratch in chunks
+// of frames (jpeg_chunk_frames).
+int32_t jpeg_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int quality, bool bw, uint8_t* out,
+                  int64_t out_stride, int64_t out_capacity, uint32_t* sizes, int16_t* coeffs, hipStream_t s);
+// "" when the encoder takes the frame: height % 8 == 0 (the reference's block
+// walk reads past the planes otherwise), both sides at most 65535 (SOF0), and a
+// worst-case stream below 2^31 bytes
+std::string jpeg_geometry_error(int64_t width, int64_t height);
 
 }  // namespace trik_hsv
 #pragma GCC visibility pop

@@ -403,6 +403,55 @@ int launch_mxn_preview(const MxnPreviewArgs& a, hipStream_t s);
 constexpr int kMxnColors = 32 * 4 * 4;
 const uint32_t* mxn_color_table();
 
+// ov7670 JPEG encoder of N frames (trik_hsv_jpeg.hip), JENC =
+// trik/ov7670/jpeg_encoder/include/internal/jpeg_encoder_reference.hpp.  A
+// data unit (DU) is one 8x8 block of one component; a frame's DUs are ordered
+// block by block in raster order, Y then U then V within a block.
+constexpr int kJpegMaxHeader = 608;    // 607 bytes in colour, 324 in black and white
+constexpr int kJpegMaxDuBits = 1664;   // DC 11 + 11, 63 ACs of at most 16 + 10 bits: 1660, rounded up
+constexpr int kJpegChunkBytes = 1024;  // unstuffed bytes one workgroup counts and scatters at a time
+struct JpegHuffman {  // the four Annex K.3 tables as the reference builds them (JENC:286-315);
+  uint16_t ac_code[2][256];  // [0] luminance, [1] chrominance; an undefined
+  uint8_t ac_len[2][256];    // symbol has length 0 and writes no bits
+  uint16_t dc_code[2][12];
+  uint8_t dc_len[2][12];
+};
+struct JpegDivisors {
+  double fd[2][64];  // fdtbl_Y, fdtbl_UV (JENC:268-278), natural order
+};
+struct JpegHeader {
+  uint8_t bytes[kJpegMaxHeader];
+  int32_t size;
+};
+struct JpegArgs {
+  const uint8_t* frames;
+  int64_t frame_stride;
+  int32_t n_frames, width, height, line_length;
+  int32_t aligned4;
+  int32_t ncomp;               // 3, or 1 in black and white
+  int32_t blocks_w;            // width / 8
+  uint32_t n_du;               // DUs per frame
+  const JpegHuffman* huff;     // device copy of jpeg_huffman()
+  int16_t* coeffs;             // [n][n_du][64] quantised coefficients, zigzag order
+  uint32_t* info;              // [n][n_du]: AC bits | DC << 16
+  unsigned long long* bitoff;  // [n][n_du]: the DU's first bit in the frame's entropy-coded segment
+  unsigned long long* total;   // [n]: the frame's entropy-coded bits before the fill bits
+  uint32_t* words;             // [n][words_per_frame]: the unstuffed segment, big-endian bit order
+  uint64_t words_per_frame;    // a multiple of kJpegChunkBytes / 4
+  uint32_t* chunk_ff;          // [n][chunks_per_frame]: 0xFF bytes per chunk, then their exclusive scan
+  uint32_t chunks_per_frame;
+  uint8_t* out;                // NULL: sizes only
+  int64_t out_stride, out_capacity;
+  uint32_t* sizes;             // [n]
+};
+// the whole pipeline for a.n_frames frames on s; a.n_frames * n_du < 2^31
+int launch_jpeg(const JpegArgs& a, const JpegDivisors& d, const JpegHeader& hd, hipStream_t s);
+// Host tables (trik_hsv_tables.cpp).  quality is clamped to 1..100 (JENC:771-786).
+const JpegHuffman* jpeg_huffman();
+void jpeg_quant_tables(int quality, uint8_t* lum_natural, uint8_t* chr_natural);
+void jpeg_divisors(int quality, JpegDivisors& d);
+void jpeg_header(int quality, bool bw, int width, int height, JpegHeader& hd);
+
 // Host side of the preview geometry (trik_hsv_tables.cpp): the reference's
 // scale maps and their inverses, packed as
 //   wi2wo[width], hi2ho[height], last_row[out_h], last_col[out_w]  (32-bit each).

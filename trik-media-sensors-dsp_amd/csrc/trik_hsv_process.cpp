@@ -165,10 +165,34 @@ int32_t process_mxn(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewOu
   return 0;
 }
 
+// JPGEncoderWrapper::run, JWRAP:52-77: the stream into the caller's output
+// buffer (`out`, `cap` bytes; NULL: no output stream, the size alone) and its
+// length into OutArgs.  A stream longer than the buffer fails the run with
+// nothing of it written (the reference writes on past the buffer).
+int32_t process_jpeg(TrikCvHandle* h, const TrikHsvFrameBatch& b, int8_t* out, int64_t cap, int quality, bool bw,
+                     TRIK_VIDTRANSCODE_CV_JPEG_OutArgsAlg& oa) {
+  if (!h->d_jpeg_size) HIP_TRY(hipMalloc(&h->d_jpeg_size, sizeof(uint32_t)));
+  int32_t r = jpeg_core(h, b, quality, bw, out ? h->d_preview : nullptr, cap, cap, h->d_jpeg_size, nullptr,
+                        h->stream);
+  if (r) return r;
+  uint32_t size = 0;
+  HIP_TRY(hipMemcpyAsync(&size, h->d_jpeg_size, sizeof size, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (out) {
+    if ((int64_t)size > cap)
+      return fail(TRIK_IVIDTRANSCODE_EFAIL, "the JPEG stream (" + std::to_string(size) +
+                                                " bytes) is longer than the output buffer");
+    HIP_TRY(hipMemcpyAsync(out, h->d_preview, size, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  }
+  oa.size = size;
+  return 0;
+}
+
 // The algorithm's run on a checked frame: the targets cleared, then a frame
 // of non-zero size staged and taken through the handle's sensor.
-int32_t run_sensor(TrikCvHandle* h, const void* frame, const PreviewOut& pv, const TRIK_VIDTRANSCODE_CV_InArgs* in_args,
-                   TRIK_VIDTRANSCODE_CV_OutArgs* out_args) {
+int32_t run_sensor(TrikCvHandle* h, const void* frame, const PreviewOut& pv, int64_t out_cap,
+                   const TRIK_VIDTRANSCODE_CV_InArgs* in_args, TRIK_VIDTRANSCODE_CV_OutArgs* out_args) {
   TRIK_VIDTRANSCODE_CV_OutArgsAlg& oa = out_args->alg;
   auto* ia7 = reinterpret_cast<const TRIK_VIDTRANSCODE_CV_OV7670_InArgs*>(in_args);
   auto* oa7 = reinterpret_cast<TRIK_VIDTRANSCODE_CV_OV7670_OutArgs*>(out_args);
@@ -187,6 +211,21 @@ int32_t run_sensor(TrikCvHandle* h, const void* frame, const PreviewOut& pv, con
     TrikHsvFrameBatch b;
     const int32_t r = stage_frame(h, frame, pv.bytes, b);
     return r ? r : process_mxn(h, b, pv, im.widthM, im.heightN, om);
+  }
+  if (h->algo == kAlgoJpeg) {
+    const auto& ij = reinterpret_cast<const TRIK_VIDTRANSCODE_CV_JPEG_InArgs*>(in_args)->alg;
+    auto& oj = reinterpret_cast<TRIK_VIDTRANSCODE_CV_JPEG_OutArgs*>(out_args)->alg;
+    if (h->in_w <= 0 || h->in_h <= 0) return 0;  // nothing is encoded, size is left untouched (JWRAP:67)
+    // The block walk is checked here, the reference does not (a height that
+    // is no multiple of 8 reads past both planes): such a frame fails the run.
+    const std::string e = jpeg_geometry_error(h->in_w, h->in_h);
+    if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+    DeviceGuard dg(h->device);
+    TrikHsvFrameBatch b;
+    // (the stream is staged in d_preview: the caller's whole buffer is its capacity)
+    const int64_t cap = pv.ptr && out_cap > 0 ? out_cap : 0;
+    const int32_t r = stage_frame(h, frame, (size_t)cap, b);
+    return r ? r : process_jpeg(h, b, pv.ptr, cap, ij.jpgImageQuality, ij.ifBlackAndWhite != 0, oj);
   }
   if (h->algo == kAlgoBlob)
     memset(oa7->alg.target, 0, sizeof oa7->alg.target);  // OSEQ:563
@@ -216,14 +255,16 @@ extern "C" int32_t TRIK_VIDTRANSCODE_CV_process(TRIK_VIDTRANSCODE_CV_Handle h,
   if (!h || !in_bufs || !out_bufs || !in_args || !out_args)
     return fail(TRIK_IVIDTRANSCODE_EFAIL, "NULL argument");
   std::lock_guard<std::mutex> lock(h->mu);
-  // the ov7670 object sensor and the MxN sensor have their own InArgs / OutArgs
-  const bool blob = h->algo == kAlgoBlob, mxn = h->algo == kAlgoMxn;
-  const int32_t in_want = blob  ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_InArgs)
-                          : mxn ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_MXN_InArgs)
-                                : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_InArgs);
-  const int32_t out_want = blob  ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_OutArgs)
-                           : mxn ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_MXN_OutArgs)
-                                 : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OutArgs);
+  // the ov7670 object sensor, the MxN sensor and the JPEG encoder have their own InArgs / OutArgs
+  const bool blob = h->algo == kAlgoBlob, mxn = h->algo == kAlgoMxn, jpeg = h->algo == kAlgoJpeg;
+  const int32_t in_want = blob   ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_InArgs)
+                          : mxn  ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_MXN_InArgs)
+                          : jpeg ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_JPEG_InArgs)
+                                 : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_InArgs);
+  const int32_t out_want = blob   ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OV7670_OutArgs)
+                           : mxn  ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_MXN_OutArgs)
+                           : jpeg ? (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_JPEG_OutArgs)
+                                  : (int32_t)sizeof(TRIK_VIDTRANSCODE_CV_OutArgs);
   if (in_args->base.size != in_want ||  // WFXNS:192-197
       out_args->base.size != out_want) {
     set_bit(out_args->base.extendedError, TRIK_XDM_UNSUPPORTEDPARAM_BIT);
@@ -271,9 +312,10 @@ extern "C" int32_t TRIK_VIDTRANSCODE_CV_process(TRIK_VIDTRANSCODE_CV_Handle h,
     rc = TRIK_IVIDTRANSCODE_EFAIL; why = "output buffer smaller than the preview";  // WSEQ:417-418
   }
   if (rc == TRIK_IVIDTRANSCODE_EOK) {
+    const int64_t out_cap = out_size;  // the caller's buffer (the JPEG encoder's capacity)
     out_size = (int64_t)h->out_h * h->out_ll;  // WSEQ:419
     const PreviewOut pv = {out_ptr, out_ptr && out_size > 0 ? (size_t)out_size : 0};
-    if (run_sensor(h, in->buf, pv, in_args, out_args)) { rc = TRIK_IVIDTRANSCODE_EFAIL; why = last_error(); }
+    if (run_sensor(h, in->buf, pv, out_cap, in_args, out_args)) { rc = TRIK_IVIDTRANSCODE_EFAIL; why = last_error(); }
   }
   if (rc != TRIK_IVIDTRANSCODE_EOK) {
     set_bit(out_args->base.extendedError, TRIK_XDM_CORRUPTEDDATA_BIT);  // WFXNS:243-247

@@ -423,6 +423,119 @@ int32_t trik_hsv::mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, 
   return note_uses(h, nullptr, true, s);
 }
 
+std::string trik_hsv::jpeg_geometry_error(int64_t width, int64_t height) {
+  if (height % 8 != 0)
+    return "the JPEG encoder takes height % 8 == 0 (the reference's block walk reads past the planes otherwise)";
+  if (width > 65535 || height > 65535) return "the JPEG encoder takes width, height <= 65535 (SOF0 holds 16 bits)";
+  // stream lengths are 32-bit (OutArgs size): header + worst-case segment, every byte stuffed, + EOI
+  if ((width / 8) * (height / 8) * 3 * (kJpegMaxDuBits / 8) * 2 + kJpegMaxHeader + 4 > 0x7FFFFFFFll)
+    return "the JPEG encoder's worst-case stream of this frame exceeds 2^31 bytes";
+  return "";
+}
+
+namespace {
+
+constexpr size_t kJpegScratchBudget = 256u << 20;  // scratch of one chunk of frames, unless one frame needs more
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The scratch of one chunk of `frames` frames, as offsets into d_jpeg_scratch.
+struct JpegScratch {
+  size_t coeffs, info, bitoff, total, words, chunk_ff, bytes;
+  uint64_t words_per_frame;
+  uint32_t chunks_per_frame;
+  JpegScratch(size_t frames, size_t n_du) {
+    // a DU takes at most kJpegMaxDuBits bits; two more words for the fill
+    // bits' byte and the zeroing's margin; whole chunks
+    const uint64_t w = ((uint64_t)n_du * kJpegMaxDuBits + 31) / 32 + 2;
+    chunks_per_frame = (uint32_t)((w * 4 + kJpegChunkBytes - 1) / kJpegChunkBytes);
+    words_per_frame = (uint64_t)chunks_per_frame * (kJpegChunkBytes / 4);
+    size_t o = 0;
+    coeffs = o; o += align256(frames * n_du * 64 * sizeof(int16_t));
+    info = o; o += align256(frames * n_du * sizeof(uint32_t));
+    bitoff = o; o += align256(frames * n_du * sizeof(unsigned long long));
+    total = o; o += align256(frames * sizeof(unsigned long long));
+    words = o; o += align256(frames * words_per_frame * sizeof(uint32_t));
+    chunk_ff = o; o += align256(frames * chunks_per_frame * sizeof(uint32_t));
+    bytes = o;
+  }
+};
+
+// Frames per chunk: as many as the budget holds, at least one, and within the
+// launch limits (2^31 DUs per launch, 65535 in a grid's second dimension).
+int64_t jpeg_chunk_frames(int64_t n_frames, size_t n_du) {
+  const size_t one = JpegScratch(1, n_du).bytes;
+  int64_t f = (int64_t)(kJpegScratchBudget / one);
+  const int64_t by_du = (int64_t)(0x7FFFFFFFull / n_du);
+  if (f > by_du) f = by_du;
+  if (f > 32768) f = 32768;
+  if (f > n_frames) f = n_frames;
+  return f < 1 ? 1 : f;
+}
+
+}  // namespace
+
+// JPGEncoder::encode of every frame (JENC:802-852).  The header is built on
+// the host and travels as a kernel argument, like the divisor tables.
+int32_t trik_hsv::jpeg_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int quality, bool bw, uint8_t* out,
+                            int64_t out_stride, int64_t out_capacity, uint32_t* sizes, int16_t* coeffs,
+                            hipStream_t s) {
+  if (!h->d_jpeg_huff) {  // once per handle; the host table is static
+    JpegHuffman* t = nullptr;
+    HIP_TRY(hipMalloc(&t, sizeof(JpegHuffman)));
+    hipError_t e = hipMemcpyAsync(t, jpeg_huffman(), sizeof(JpegHuffman), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // later calls may run on other streams
+    if (e != hipSuccess) {
+      (void)hipFree(t);
+      return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("JPEG Huffman table upload: ") + hipGetErrorString(e));
+    }
+    h->d_jpeg_huff = t;
+  }
+  const int ncomp = bw ? 1 : 3;
+  const size_t n_du = (size_t)(b.width / 8) * (size_t)(b.height / 8) * ncomp;
+  const int64_t chunk = jpeg_chunk_frames(b.n_frames, n_du);
+  const JpegScratch sc((size_t)chunk, n_du);
+  if (sc.bytes > h->d_jpeg_scratch_cap) h->jpeg_users.wait_all();  // the buffer is replaced
+  HIP_TRY(h->jpeg_users.order_after(s));
+  int32_t r = grow(h->d_jpeg_scratch, h->d_jpeg_scratch_cap, sc.bytes);
+  if (r) return r;
+
+  JpegDivisors dv;
+  JpegHeader hd;
+  jpeg_divisors(quality, dv);
+  jpeg_header(quality, bw, b.width, b.height, hd);
+  JpegArgs a;
+  a.frame_stride = b.frame_stride;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  a.aligned4 = aligned4(b);
+  a.ncomp = ncomp;
+  a.blocks_w = b.width / 8;
+  a.n_du = (uint32_t)n_du;
+  a.huff = h->d_jpeg_huff;
+  uint8_t* base = h->d_jpeg_scratch;
+  a.coeffs = reinterpret_cast<int16_t*>(base + sc.coeffs);
+  a.info = reinterpret_cast<uint32_t*>(base + sc.info);
+  a.bitoff = reinterpret_cast<unsigned long long*>(base + sc.bitoff);
+  a.total = reinterpret_cast<unsigned long long*>(base + sc.total);
+  a.words = reinterpret_cast<uint32_t*>(base + sc.words);
+  a.words_per_frame = sc.words_per_frame;
+  a.chunk_ff = reinterpret_cast<uint32_t*>(base + sc.chunk_ff);
+  a.chunks_per_frame = sc.chunks_per_frame;
+  a.out_stride = out_stride;
+  a.out_capacity = out_capacity;
+  for (int64_t f0 = 0; f0 < b.n_frames; f0 += chunk) {
+    a.n_frames = (int32_t)(b.n_frames - f0 < chunk ? b.n_frames - f0 : chunk);
+    a.frames = static_cast<const uint8_t*>(b.frames) + f0 * b.frame_stride;
+    a.out = out ? out + f0 * out_stride : nullptr;
+    a.sizes = sizes + f0;
+    HIP_TRY(launch_jpeg(a, dv, hd, s));
+    if (coeffs)  // the verification output: the chunk's coefficients as the block kernel left them
+      HIP_TRY(hipMemcpyAsync(coeffs + f0 * (int64_t)n_du * 64, a.coeffs,
+                             (size_t)a.n_frames * n_du * 64 * sizeof(int16_t), hipMemcpyDeviceToDevice, s));
+  }
+  return note_uses(h, nullptr, false, s, &h->jpeg_users);
+}
+
 int32_t trik_hsv::blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta,
                                     const int32_t* top, int ow, int oh, int oll, uint8_t* previews, int64_t stride,
                                     hipStream_t s) {

@@ -185,6 +185,158 @@ const uint32_t* mxn_color_table() {
   return t.c;
 }
 
+// ---------------------------------------------------------------------------
+// The JPEG encoder's tables (JENC:244-315, 517-647): ITU-T T.81 Annex K.1
+// quantisers and Annex K.3 Huffman tables, retyped from the standard.
+// ---------------------------------------------------------------------------
+namespace {
+
+const uint8_t kJpegQLum[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
+                               14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                               18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                               49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+const uint8_t kJpegQChr[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+                               24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                               99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                               99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+const uint8_t kJpegDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
+                                    {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kJpegAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
+                                    {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
+// HUFFVAL of the two AC tables: an irregular head, then runs r2..rA (or r1..rA)
+const uint8_t kJpegAcLumHead[] = {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41,
+                                  0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91,
+                                  0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24,
+                                  0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a};
+const uint8_t kJpegAcLumRuns[][2] = {{0x25, 0x2a}, {0x34, 0x3a}, {0x43, 0x4a}, {0x53, 0x5a}, {0x63, 0x6a},
+                                     {0x73, 0x7a}, {0x83, 0x8a}, {0x92, 0x9a}, {0xa2, 0xaa}, {0xb2, 0xba},
+                                     {0xc2, 0xca}, {0xd2, 0xda}, {0xe1, 0xea}, {0xf1, 0xfa}};
+const uint8_t kJpegAcChrHead[] = {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41,
+                                  0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91,
+                                  0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
+                                  0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a};
+const uint8_t kJpegAcChrRuns[][2] = {{0x26, 0x2a}, {0x35, 0x3a}, {0x43, 0x4a}, {0x53, 0x5a}, {0x63, 0x6a},
+                                     {0x73, 0x7a}, {0x82, 0x8a}, {0x92, 0x9a}, {0xa2, 0xaa}, {0xb2, 0xba},
+                                     {0xc2, 0xca}, {0xd2, 0xda}, {0xe2, 0xea}, {0xf2, 0xfa}};
+// the eight AAN scale factors as the reference's decimal literals (JENC:207-210)
+const double kJpegAasf[8] = {1.0, 1.387039845, 1.306562965, 1.175875602, 1.0, 0.785694958, 0.541196100, 0.275899379};
+
+struct JpegStatic {
+  JpegHuffman huff;
+  uint8_t ac_vals[2][162];
+  uint8_t zz[64];  // zz[natural index] = position in the zigzag scan
+  JpegStatic() {
+    memset(&huff, 0, sizeof huff);
+    int n = 0;
+    for (uint8_t v : kJpegAcLumHead) ac_vals[0][n++] = v;
+    for (const auto& r : kJpegAcLumRuns)
+      for (int v = r[0]; v <= r[1]; ++v) ac_vals[0][n++] = (uint8_t)v;
+    n = 0;
+    for (uint8_t v : kJpegAcChrHead) ac_vals[1][n++] = v;
+    for (const auto& r : kJpegAcChrRuns)
+      for (int v = r[0]; v <= r[1]; ++v) ac_vals[1][n++] = (uint8_t)v;
+    for (int t = 0; t < 2; ++t) {  // computeHuffmanTbl, JENC:286-307
+      int code = 0, pos = 0;
+      for (int k = 1; k <= 16; ++k) {
+        for (int j = 0; j < kJpegDcBits[t][k - 1]; ++j, ++pos, ++code) {
+          huff.dc_code[t][pos] = (uint16_t)code;  // the DC symbols are 0..11 in order
+          huff.dc_len[t][pos] = (uint8_t)k;
+        }
+        code *= 2;
+      }
+      code = 0; pos = 0;
+      for (int k = 1; k <= 16; ++k) {
+        for (int j = 0; j < kJpegAcBits[t][k - 1]; ++j, ++pos, ++code) {
+          huff.ac_code[t][ac_vals[t][pos]] = (uint16_t)code;
+          huff.ac_len[t][ac_vals[t][pos]] = (uint8_t)k;
+        }
+        code *= 2;
+      }
+    }
+    int r = 0, c = 0;  // the zigzag walk of T.81 figure A.6
+    for (int k = 0; k < 64; ++k) {
+      zz[8 * r + c] = (uint8_t)k;
+      if (((r + c) & 1) == 0) {
+        if (c == 7) ++r; else if (r == 0) ++c; else { --r; ++c; }
+      } else {
+        if (r == 7) ++c; else if (c == 0) ++r; else { ++r; --c; }
+      }
+    }
+  }
+};
+const JpegStatic& jpeg_static() {
+  static const JpegStatic t;  // built once, on first use
+  return t;
+}
+
+}  // namespace
+
+const JpegHuffman* jpeg_huffman() { return &jpeg_static().huff; }
+
+void jpeg_quant_tables(int quality, uint8_t* lum, uint8_t* chr) {  // JENC:244-267, 771-786
+  const int q = quality <= 0 ? 1 : (quality > 100 ? 100 : quality);
+  const int sf = q < 50 ? 5000 / q : 200 - q * 2;
+  for (int i = 0; i < 64; ++i) {
+    const int l = (kJpegQLum[i] * sf + 50) / 100, c = (kJpegQChr[i] * sf + 50) / 100;
+    lum[i] = (uint8_t)(l < 1 ? 1 : (l > 255 ? 255 : l));
+    chr[i] = (uint8_t)(c < 1 ? 1 : (c > 255 ? 255 : c));
+  }
+}
+
+// fdtbl of JENC:268-278: each product rounded on its own, left to right
+void jpeg_divisors(int quality, JpegDivisors& d) {
+#pragma clang fp contract(off)
+  uint8_t q[2][64];
+  jpeg_quant_tables(quality, q[0], q[1]);
+  for (int t = 0; t < 2; ++t)
+    for (int row = 0; row < 8; ++row)
+      for (int col = 0; col < 8; ++col) {
+        const double a = (double)q[t][8 * row + col] * kJpegAasf[row];
+        const double b = a * kJpegAasf[col];
+        d.fd[t][8 * row + col] = 1.0 / (b * 8.0);
+      }
+}
+
+// SOI, APP0, DQT, SOF0, DHT, SOS (JENC:517-647, 811-817)
+void jpeg_header(int quality, bool bw, int width, int height, JpegHeader& hd) {
+  const JpegStatic& st = jpeg_static();
+  uint8_t q[2][64];
+  jpeg_quant_tables(quality, q[0], q[1]);
+  int n = 0;
+  uint8_t* o = hd.bytes;
+  auto byte = [&](int v) { o[n++] = (uint8_t)v; };
+  auto word = [&](int v) { byte(v >> 8); byte(v); };
+  word(0xFFD8);
+  word(0xFFE0); word(16);
+  for (char ch : {'J', 'F', 'I', 'F', '\0'}) byte(ch);
+  byte(1); byte(1); byte(0); word(1); word(1); byte(0); byte(0);
+  word(0xFFDB); word(bw ? 67 : 132);
+  for (int t = 0; t < (bw ? 1 : 2); ++t) {  // the DQT carries the quantisers in zigzag order
+    byte(t);
+    uint8_t z[64];
+    for (int i = 0; i < 64; ++i) z[st.zz[i]] = q[t][i];
+    for (int i = 0; i < 64; ++i) byte(z[i]);
+  }
+  word(0xFFC0); word(bw ? 11 : 17); byte(8); word(height); word(width);
+  byte(bw ? 1 : 3);
+  byte(1); byte(0x11); byte(0);
+  if (!bw) { byte(2); byte(0x11); byte(1); byte(3); byte(0x11); byte(1); }
+  word(0xFFC4); word(bw ? 0xD2 : 0x01A2);
+  for (int t = 0; t < (bw ? 1 : 2); ++t) {
+    byte(t);
+    for (int i = 0; i < 16; ++i) byte(kJpegDcBits[t][i]);
+    for (int i = 0; i < 12; ++i) byte(i);
+    byte(0x10 | t);
+    for (int i = 0; i < 16; ++i) byte(kJpegAcBits[t][i]);
+    for (int i = 0; i < 162; ++i) byte(st.ac_vals[t][i]);
+  }
+  word(0xFFDA);
+  if (bw) { word(8); byte(1); byte(1); byte(0); }
+  else { word(12); byte(3); byte(1); byte(0); byte(2); byte(0x11); byte(3); byte(0x11); }
+  byte(0); byte(0x3F); byte(0);
+  hd.size = n;
+}
+
 void auto_range_zone(int width, int height, int32_t& c_lo, int32_t& c_hi, int32_t& r_lo, int32_t& r_hi) {
   // HsvRangeDetector::initImg (cv_hsv_range_detector.hpp:88-108), zone scale 6
   // (WSEQ:32): uint16_t fields, so differences wrap modulo 2^16.

@@ -318,6 +318,39 @@ class Detector(_HotKernel):
             raise TrikHsvError(rc, "trik_hsv_mxn_preview")
         return previews
 
+    def jpeg_batch(self, frames, width, height, line_length, quality, black_and_white=False, *, capacity=None,
+                   out_stride=None, n_frames=None, frame_stride=None, coeffs=False, sizes_only=False,
+                   out=None, stream=None):
+        """The ov7670 JPEG encoder over N frames (JENC:802-852).  Returns
+        (streams, sizes[, coeffs]): streams uint8 [N, out_stride] (frame i's
+        stream is streams[i, :sizes[i]]; a stream longer than `capacity` is not
+        written; None with sizes_only), sizes int32 [N] (always the full
+        lengths), coeffs int16 [N, blocks, components, 64] (quantised, zigzag
+        order) when asked.  `capacity` defaults to the worst case of the
+        geometry; `out` is a caller's uint8 tensor to write into instead of a
+        fresh one (its rows are then `out_stride` apart)."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
+        ncomp = 1 if black_and_white else 3
+        blocks = (width // 8) * (height // 8)
+        if capacity is None:  # header + every data unit at its longest, every byte stuffed + EOI
+            capacity = 608 + 2 * (blocks * ncomp * 208 + 1) + 2
+        stride = int(capacity) if out_stride is None else int(out_stride)
+        streams = None
+        if not sizes_only:
+            streams = out if out is not None else torch.empty((b.n_frames, stride), dtype=torch.uint8,
+                                                              device=frames.device)
+        sizes = torch.empty((b.n_frames,), dtype=torch.int32, device=frames.device)
+        co = torch.empty((b.n_frames, blocks, ncomp, 64), dtype=torch.int16, device=frames.device) if coeffs else None
+        rc = _lib.trik_hsv_jpeg_batch(self._h, C.byref(b), int(quality), int(bool(black_and_white)),
+                                      C.c_void_p(streams.data_ptr()) if streams is not None else None, stride,
+                                      int(capacity), C.c_void_p(sizes.data_ptr()),
+                                      C.c_void_p(co.data_ptr()) if coeffs else None, _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_jpeg_batch")
+        return (streams, sizes, co) if coeffs else (streams, sizes)
+
     def line_preview(self, frames, width, height, line_length, val_from, val_to, sums, *,
                      out_width=None, out_height=None, out_line_length=None, n_frames=None,
                      frame_stride=None, stream=None):
@@ -362,6 +395,16 @@ def mxn_color(h: int, s: int, v: int) -> int:
     """The MxN sensor's 0x00RRGGBB colour of histogram bin (h 0..31, s 0..3,
     v 0..3): trik_hsv_mxn_color, host code."""
     return int(_lib.trik_hsv_mxn_color(int(h), int(s), int(v)))
+
+
+def jpeg_header(quality: int, black_and_white: bool, width: int, height: int) -> bytes:
+    """The JPEG encoder's header (SOI .. SOS) for a width x height frame:
+    trik_hsv_jpeg_header, host code."""
+    buf = (C.c_uint8 * 608)()
+    n = int(_lib.trik_hsv_jpeg_header(int(quality), int(bool(black_and_white)), int(width), int(height), buf, 608))
+    if n <= 0:
+        raise TrikHsvError(IVIDTRANSCODE_EFAIL, "trik_hsv_jpeg_header")
+    return bytes(buf[:n])
 
 
 def batch_auto_range(frames, width, height, line_length, layout, *, n_frames=None,
@@ -721,3 +764,37 @@ class MxnSensor(ObjectSensor):
         rc = _lib.TRIK_VIDTRANSCODE_CV_process(self._h, C.byref(ib), C.byref(ob), C.byref(ia), C.byref(oa))
         colors = list(oa.alg.outColor[: int(m) * int(n)]) if rc == IVIDTRANSCODE_EOK else None
         return rc, oa, colors
+
+
+class JpegSensor(ObjectSensor):
+    """The ov7670 JPEG encoder's codec instance (trik/ov7670/jpeg_encoder:
+    JPGEncoderWrapper<YUV422P, RGB565X> behind the ov7670 object sensor's
+    glue): its own InArgs (jpgImageQuality, ifBlackAndWhite) and OutArgs
+    (size).  The output buffer receives the JPEG stream."""
+
+    _create = "TRIK_VIDTRANSCODE_CV_create_jpeg"
+
+    def __init__(self, params: _abi.Params | None = None):
+        super().__init__(params)
+        if params is None:
+            self.params = _default_params(1, fmt_in=FORMAT_YUV422P)
+
+    def process(self, frame, quality, black_and_white=False, out_buffer=None, num_bytes=None, input_id=0,
+                out_args=None):
+        """One host frame -> (rc, JpegOutArgs, stream): stream is the JPEG's
+        bytes from out_buffer (None unless rc is EOK and there is a buffer).
+        `out_args`: a prepared JpegOutArgs to fill instead of a fresh one."""
+        fr, ib, ob, keep = self._bufs(frame, out_buffer, num_bytes)
+        ia = _abi.JpegInArgs()
+        ia.base.size = C.sizeof(_abi.JpegInArgs)
+        ia.base.numBytes = fr.size if num_bytes is None else num_bytes
+        ia.base.inputID = input_id
+        ia.alg = _abi.JpegInArgsAlg(int(quality) & 0xFF, int(bool(black_and_white)))
+        oa = out_args if out_args is not None else _abi.JpegOutArgs()
+        if out_args is None:
+            oa.base.size = C.sizeof(_abi.JpegOutArgs)
+        rc = _lib.TRIK_VIDTRANSCODE_CV_process(self._h, C.byref(ib), C.byref(ob), C.byref(ia), C.byref(oa))
+        stream = None
+        if rc == IVIDTRANSCODE_EOK and out_buffer is not None:
+            stream = bytes(out_buffer.reshape(-1).view("uint8")[: int(oa.alg.size)])
+        return rc, oa, stream

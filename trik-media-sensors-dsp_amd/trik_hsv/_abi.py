@@ -118,6 +118,17 @@ class MxnOutArgsAlg(C.Structure):
     _fields_ = [("outColor", i32 * 100)]
 
 
+class JpegInArgsAlg(C.Structure):
+    """TRIK_VIDTRANSCODE_CV_JPEG_InArgsAlg (ov7670 jpeg_encoder trik_vidtranscode_cv.h:49-52);
+    XDAS_Bool is a 32-bit int."""
+    _fields_ = [("jpgImageQuality", C.c_uint8), ("ifBlackAndWhite", i32)]
+
+
+class JpegOutArgsAlg(C.Structure):
+    """TRIK_VIDTRANSCODE_CV_JPEG_OutArgsAlg (ov7670 jpeg_encoder trik_vidtranscode_cv.h:60-62)."""
+    _fields_ = [("size", C.c_uint32)]
+
+
 class SingleBufDesc(C.Structure):
     _fields_ = [("buf", C.c_void_p), ("bufSize", i32), ("accessMask", i32)]
 
@@ -159,6 +170,14 @@ class MxnOutArgs(C.Structure):
     _fields_ = [("base", IVidtranscodeOutArgs), ("alg", MxnOutArgsAlg)]
 
 
+class JpegInArgs(C.Structure):
+    _fields_ = [("base", IVidtranscodeInArgs), ("alg", JpegInArgsAlg)]
+
+
+class JpegOutArgs(C.Structure):
+    _fields_ = [("base", IVidtranscodeOutArgs), ("alg", JpegOutArgsAlg)]
+
+
 class AlgBufInfo(C.Structure):
     _fields_ = [("minNumInBufs", i32), ("minNumOutBufs", i32),
                 ("minInBufSize", i32 * MAX_IO_BUFFERS), ("minOutBufSize", i32 * MAX_IO_BUFFERS)]
@@ -189,10 +208,11 @@ PROTOTYPES = {
     "TRIK_VIDTRANSCODE_CV_create_ov7670": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_create_webcam_line": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_create_mxn": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
+    "TRIK_VIDTRANSCODE_CV_create_jpeg": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_delete": ([C.c_void_p], i32),
     # InArgs / OutArgs by pointer: the webcam structs, the OV7670 ones for a
-    # create_ov7670 handle or the MXN ones for a create_mxn handle (their
-    # base.size fields say which)
+    # create_ov7670 handle, the MXN ones for a create_mxn handle or the JPEG
+    # ones for a create_jpeg handle (their base.size fields say which)
     "TRIK_VIDTRANSCODE_CV_process": ([C.c_void_p, C.POINTER(BufDesc1), C.POINTER(BufDesc),
                                       C.c_void_p, C.c_void_p], i32),
     "TRIK_VIDTRANSCODE_CV_control": ([C.c_void_p, i32, C.POINTER(DynamicParams),
@@ -225,6 +245,9 @@ PROTOTYPES = {
     "trik_hsv_mxn_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,
                               C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_mxn_color": ([i32, i32, i32], C.c_uint32),
+    "trik_hsv_jpeg_batch": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, C.c_int64, C.c_int64,
+                             C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_jpeg_header": ([i32, i32, i32, i32, C.c_void_p, i32], i32),
     "trik_hsv_synth": ([C.POINTER(FrameBatch), i32, i32, u64, C.c_void_p], i32),
     "trik_hsv_set_hot_kernel": ([C.c_void_p, i32], i32),
     "trik_hsv_last_hot_kernel": ([C.c_void_p], i32),

@@ -20,11 +20,16 @@
  * tests/test_oracle.py requires them to agree on all 2^24 inputs.
  *
  * PARITY STATUS: the reference ships no tests, fixtures or golden vectors,
- * and its hot path cannot be compiled here (it needs TI's <c6x.h> and the
- * XDAIS headers, which are absent; building it with stand-in headers is not
- * allowed).  Parity is therefore "unpinned" by reference artefacts.  It is
- * pinned instead by the two derivations above, per-intrinsic unit tests and
- * the SURVEY Appendix A known-answer table.  See DESIGN.md section 3.
+ * and there is no TI compiler here.  The intrinsics below therefore remain
+ * emulations from TI's documented semantics, held by per-intrinsic
+ * known-answer tests.  Everything the reference builds on top of them is
+ * pinned to the reference's own code: oracle/ref compiles its algorithm
+ * classes on the host over a shim <c6x.h> that maps the intrinsics onto these
+ * emulations, and tests/test_reference_cpu.py requires every function of
+ * this header that restates a run() -- and the per-pixel table on all 2^24
+ * inputs -- to equal what those classes compute (the one divergence, the
+ * order of equal-sized clusters, is described at trik_oracle_blob_run).  The
+ * XDAIS function table is not built.  See DESIGN.md section 2.
  */
 #ifndef TRIK_ORACLE_H_
 #define TRIK_ORACLE_H_

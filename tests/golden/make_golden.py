@@ -10,8 +10,13 @@ What the fixture holds (inputs are regenerated from seeds, not stored):
     expected per-range {N, sumX, sumY} and {targetX, targetY, targetSize}.
 
 These vectors are produced by the repo's own restatement of the reference
-(the reference ships none and cannot be built here -- DESIGN.md section 3),
-so they pin regressions and the GPU path, not the reference itself.
+(the reference ships none), so by themselves they pin regressions and the GPU
+path.  The restatement is held to the reference's own code elsewhere:
+tests/test_reference_cpu.py runs the inputs of CASES, RUN_CASES, LINE_CASES and
+BLOB_CASES that the reference's 640 x 480 static images can take through its
+algorithm classes built on the host (oracle/ref), and
+tests/golden/make_reference_golden.py records vectors from those classes
+(DESIGN.md section 2).
 """
 import hashlib
 import json

@@ -37,6 +37,10 @@ def det(hsv):
 
 @pytest.fixture(scope="module")
 def yuv_of_bin(table):
+    return yuv_of_bin_map(table)
+
+
+def yuv_of_bin_map(table):
     """bin -> (Y, U, V) of the first table entry in that bin (reachable bins only)."""
     hsvw = (table & np.uint64(0xFFFFFFFF)).astype(np.int64)
     bins = (((hsvw & 255) >> 3) << 4) | ((((hsvw >> 8) & 255) >> 6) << 2) | (((hsvw >> 16) & 255) >> 6)
@@ -171,11 +175,9 @@ def crafted(yuv_of_bin, w, h, ll, m, n, cell_seqs):
     return fr
 
 
-def test_mxn_crafted_ties(hsv, det, table, yuv_of_bin):
-    """Cells holding two or three bins with equal final counts: the winner is
-    the bin that reaches the count first, whatever its index."""
-    import torch
-
+def crafted_tie_frames(yuv_of_bin):
+    """[(frame, (m, n), winning bins)] at 64 x 8: cells holding two or three
+    bins with equal final counts (shared with tests/test_reference_cpu.py)."""
     reach = sorted(yuv_of_bin)
     lo, mid, hi, fill = reach[1], reach[len(reach) // 2], reach[-2], reach[-1]
     assert lo < mid < hi
@@ -189,7 +191,15 @@ def test_mxn_crafted_ties(hsv, det, table, yuv_of_bin):
     # 64 x 8 at 1 x 1: one cell of 256 pairs, three bins at 80 pairs
     one = [hi] * 40 + [mid] * 80 + [lo] * 50 + [hi] * 40 + [lo] * 30 + [fill] * 16
     fr1 = crafted(yuv_of_bin, 64, 8, 64, 1, 1, [one])
-    for fr, (m, n), want in ((fr4, (2, 2), want4), (fr1, (1, 1), [mid])):
+    return [(fr4, (2, 2), want4), (fr1, (1, 1), [mid])]
+
+
+def test_mxn_crafted_ties(hsv, det, table, yuv_of_bin):
+    """Cells holding two or three bins with equal final counts: the winner is
+    the bin that reaches the count first, whatever its index."""
+    import torch
+
+    for fr, (m, n), want in crafted_tie_frames(yuv_of_bin):
         ref_colors, ref_bins, ties = mxn_ref.run(table, fr, 64, 8, 64, m, n)
         assert all(ties), "a crafted cell lost its tie"
         assert ref_bins == want

@@ -3,10 +3,8 @@ the oracle's restatement of its LineDetector::run (oracle/trik_oracle.c:
 trik_oracle_wline_run; LSEQW = trik/webcam/line_sensor/include/internal/
 cv_line_detector_seqpass.hpp): OutArgs and the RGB565X preview, bit-exact,
 through the XDAIS quartet (TRIK_VIDTRANSCODE_CV_create_webcam_line) and the
-exported function table.  The oracle is pinned through its shared parts (the
-per-pixel HSV and the range test, checked against the golden vectors); the
-line sensor's own composition has no reference fixture ("parity unpinned" for
-the overlay and OutArgs arithmetic beyond the restatement)."""
+exported function table.  The oracle's restatement is held to the reference's
+own LineDetector, built on the host, in tests/test_reference_cpu.py."""
 import numpy as np
 import pytest
 

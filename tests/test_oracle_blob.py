@@ -5,7 +5,7 @@ the CPU, against an independent Python restatement written from the reference
 line by line: the per-pixel table for detection, the 4x4 bitmap (BMB:171-190),
 Clusterizer::run with its vectors (CLU:44-202), std::sort by size with ties by
 label, the 8 targets (OSEQ:563-590) and the preview (OSEQ:387-420, 548-580).
-Parity unpinned (no reference fixture covers this path).
+The reference's own classes judge the same oracle in tests/test_reference_cpu.py.
 """
 import hashlib
 import math

@@ -3,8 +3,8 @@ trik/ov7670/line_sensor/include/internal/cv_line_detector_seqpass.hpp) on the
 CPU: against the committed golden runs, and against an independent numpy
 restatement built on the per-pixel table (detection by V only in columns
 5..W-5, LSEQ:283-299, 391-414; the overlays of LSEQ:88-130, 433-467; the
-OutArgs of LSEQ:452-474).  Parity unpinned (no reference fixture covers the
-line sensor); the per-pixel arithmetic it uses is the pinned one.
+OutArgs of LSEQ:452-474).  The reference's own LineDetector judges the same
+oracle in tests/test_reference_cpu.py.
 """
 import hashlib
 

@@ -421,6 +421,45 @@ int32_t TRIK_VIDTRANSCODE_CV_create_mxn(const TRIK_VIDTRANSCODE_CV_Params* param
 int32_t TRIK_VIDTRANSCODE_CV_create_jpeg(const TRIK_VIDTRANSCODE_CV_Params* params,
                                          TRIK_VIDTRANSCODE_CV_Handle* out_handle);
 
+/* The quartet for the ov7670 edge-line sensor's codec (trik/ov7670/
+ * edge_line_sensor: BallDetector<YUV422P, RGB565X> of include/internal/
+ * cv_ball_detector_seqpass.hpp -- ESEQ -- behind the ov7670 object sensor's
+ * glue; its Harris block is not compiled).  params == NULL takes that glue's
+ * defaults (YUV422P in, RGB565X out, a 320x240 output).  process() takes the
+ * webcam object sensor's InArgs and OutArgs; every InArgs field is ignored and
+ * the detect* OutArgs are left untouched.  The Y plane goes through
+ * IMG_sobel_3x3_8 and IMG_thr_gt2max_8 (threshold 50), restated from TI's
+ * documented natural-C semantics over the plane as one linear array of
+ * width * height bytes: byte i + 1 of the map is min(|H| + |V|, 255) of the
+ * 3x3 window whose first byte is i, for i in 0 .. width * (height - 2) - 3,
+ * then 255 where that exceeds the threshold.  So map (r, c) is the window
+ * with top-left (r, c - 1), columns 0 and width - 1 mix adjacent rows, and
+ * byte 0, byte width * (height - 2) - 1 and the last two rows are never
+ * written.  A pixel is detected iff its map byte is 255; per row, the count
+ * and the column sum over columns 16 .. width - 16 are uint16_t (they wrap
+ * mod 65536, the column sum from width 384) and are added to the frame's
+ * totals (ESEQ:189-205).  OutArgs (ESEQ:397-417, all 0 without a detected
+ * pixel): targetX from the mean column, targetY the frame's top (-100: the
+ * row sum stays 0), targetSize from ceil(sqrtf(points / pi)).  The preview
+ * (ESEQ:226-249, 405): IMG_ycbcr422pl_to_rgb565 of the map as luma with the
+ * frame's chroma (cb = chroma byte 2k, cr = byte 2k + 1 of pixel pair k),
+ * stored as native uint16 RGB565 -- not the byte order of the other codecs'
+ * previews --, every source pixel through the scale maps, then a line of
+ * value 0x001f at the mean column over rows height / 2 +- 99 (clamped).
+ * process() keeps this library's two-plane input check and its output-size
+ * check.  The divergences:
+ *  - inputLineLength != inputWidth is rejected by SETPARAMS (the reference
+ *    takes it and reads the padded plane as if it were dense);
+ *  - the never-written map bytes are always 0, the state of a fresh instance
+ *    (the reference keeps the map in a static, so an instance resized
+ *    downward sees stale bytes of earlier, larger frames);
+ *  - frames up to 2048 x 2048 are taken (the reference's statics hold
+ *    320 x 240 and larger frames overrun them);
+ *  - the chroma split's read of a further width * height bytes past the
+ *    frame (ESEQ:169) is not made. */
+int32_t TRIK_VIDTRANSCODE_CV_create_edge_line(const TRIK_VIDTRANSCODE_CV_Params* params,
+                                              TRIK_VIDTRANSCODE_CV_Handle* out_handle);
+
 /* Replaces TRIK_VIDTRANSCODE_CV_free (WFXNS:114-136). */
 int32_t TRIK_VIDTRANSCODE_CV_delete(TRIK_VIDTRANSCODE_CV_Handle handle);
 
@@ -501,10 +540,11 @@ typedef struct TRIK_IVIDTRANSCODE_Fxns {
 
 /* The webcam object sensor's tables (WFXNS:36-66); IALG is the same table
  * as FXNS.ialg (the reference aliases the two symbols on TI toolchains and
- * duplicates them elsewhere, as here).  The other five codecs of this library
+ * duplicates them elsewhere, as here).  The other six codecs of this library
  * (one DSP server each in the reference, all named TRIK_VIDTRANSCODE_CV_FXNS
  * there): the ov7670 object sensor, the ov7670 line sensor, the webcam line
- * sensor, the ov7670 MxN sensor and the ov7670 JPEG encoder. */
+ * sensor, the ov7670 MxN sensor, the ov7670 JPEG encoder and the ov7670
+ * edge-line sensor. */
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_FXNS;
 extern TRIK_IALG_Fxns TRIK_VIDTRANSCODE_CV_IALG;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_OV7670_FXNS;
@@ -512,6 +552,7 @@ extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_LINE_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_MXN_FXNS;
 extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_JPEG_FXNS;
+extern TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_EDGE_LINE_FXNS;
 
 /* The webcam object sensor's IALG functions (WFXNS:85-166), also reachable
  * through the tables.  alloc asks for one persistent external record (the
@@ -774,6 +815,32 @@ int32_t trik_hsv_jpeg_batch(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFra
  * large enough; 0 for a side outside 0..65535.  Host code, no GPU call. */
 int32_t trik_hsv_jpeg_header(int32_t quality, int32_t black_and_white, int32_t width, int32_t height, uint8_t* out,
                              int32_t capacity);
+
+/* The ov7670 edge-line sensor for N ov7670 frames (see
+ * TRIK_VIDTRANSCODE_CV_create_edge_line).  threshold is IMG_thr_gt2max_8's,
+ * 0..255 (the codec uses 50; with 255 a pixel is detected only where
+ * |H| + |V| >= 255).  line_length must equal width, both sides at most 2048;
+ * otherwise, or with another layout, the call fails and writes nothing.
+ *   sums_dev     [N]: {points, sum_x, 0} of ESEQ:189-205, zeroed by the call;
+ *   targets_dev  optional [N]: OutArgs targetX / targetY / targetSize;
+ *   edges_dev    optional [N][height][width] uint8: the thresholded map (the
+ *                wrap columns and the never-written zero bytes included) -- a
+ *                verification output, written by the generic kernel.
+ * No handle: nothing is cached.  Stream-ordered. */
+int32_t trik_hsv_edge_batch(const TrikHsvFrameBatch* batch, int32_t threshold, TrikHsvTargetSums* sums_dev,
+                            TrikHsvTarget* targets_dev, uint8_t* edges_dev, void* hip_stream);
+
+/* Its previews for N frames from sums_dev of trik_hsv_edge_batch with the
+ * same threshold (ESEQ:226-249, 405): zero fill, every source pixel, the
+ * target line of frames with points > 0.  uint16 RGB565 in native byte order. */
+int32_t trik_hsv_edge_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch, int32_t threshold,
+                              const TrikHsvTargetSums* sums_dev, int32_t out_width, int32_t out_height,
+                              int32_t out_line_length, uint8_t* previews_dev, int64_t preview_stride,
+                              void* hip_stream);
+
+/* The edge-line sensor's OutArgs of one frame's sums (ESEQ:397-417) for a
+ * width x height frame (each 1..2048).  Host code, no GPU call. */
+int32_t trik_hsv_edge_targets(const TrikHsvTargetSums* sums, int32_t width, int32_t height, TrikHsvTarget* target);
 
 /* Fill batch->frames (device, writable) with synthetic frames; frame i of the
  * batch is global frame first_frame + i.  kind 0 = uniform random bytes,

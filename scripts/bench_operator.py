@@ -11,6 +11,10 @@
               (2 B/px) once.  line_preview: its 320x240 previews.
   blob        trik_hsv_blob_batch: 4096 x 640x480 ov7670 frames through the
               multi-blob sensor (metapixel bitmap + clusterer + 8 targets).
+  edge        trik_hsv_edge_batch: the edge-line sensor's sums + OutArgs over
+              the same ov7670 frames and over 4096 x 320x240 ones (with the line
+              sensor on those beside it); algorithmic bytes = the Y plane once
+              (1 B/px).  sums_preview: + trik_hsv_edge_preview's 320x240 previews.
   mxn         trik_hsv_mxn_batch: the MxN colour-grid sensor over the same
               ov7670 frames at 3x3 and 10x10 cells, scene and uniform random
               bytes; algorithmic bytes = both planes once, as the line row.
@@ -117,6 +121,37 @@ def main():
                    "achieved_GBs": round(lf * lfb / (bl_ms / 1e3) / 1e9, 1),
                    "hbm_frac": round(lf * lfb / (bl_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                    "note": "bitmap (blob_chroma_meta_kernel for large batches, else blob_meta_kernel) + blob_ccl_kernel (one wave per frame)"}
+    # the edge-line sensor on the line row's frames (640x480) and on 320x240
+    # scene frames with the line sensor beside it: the sums read the Y plane only
+    out["edge"] = {"frames": lf,
+                   "note": "edge_vec_kernel + edge_targets_kernel; bytes_algorithmic = the Y plane once (1 B/px); "
+                           "line_ms: trik_hsv_line_batch on the same frames (both planes); sums_preview: + "
+                           "edge_preview_kernel into 320x240 previews"}
+    for ew, eh in ((W, H), (320, 240)):
+        edev = ldev
+        if (ew, eh) != (W, H):
+            edev = torch.empty(lf * 2 * eh * ew, dtype=torch.uint8, device="cuda")
+            trik_hsv.synth(edev, ew, eh, ew, trik_hsv.LAYOUT_OV7670, 1, 0x7A1C)
+        eln_ms = ln_ms if edev is ldev else timed(lambda: trik_hsv.line_batch(edev, ew, eh, ew, 0, 30), stream,
+                                                   args.iters)
+        ed_ms = timed(lambda: trik_hsv.edge_batch(edev, ew, eh, ew), stream, args.iters)
+        esums, _ = trik_hsv.edge_batch(edev, ew, eh, ew)
+
+        def edge_both():
+            s, _ = trik_hsv.edge_batch(edev, ew, eh, ew)
+            det.edge_preview(edev, ew, eh, ew, s, out_width=OW, out_height=OH, out_line_length=OLL)
+
+        ep_ms = timed(edge_both, stream, args.iters)
+        yb = lf * ew * eh
+        out["edge"][f"{ew}x{eh}"] = {"ms": round(ed_ms, 4), "Mframes_per_s": round(lf / ed_ms / 1e3, 3),
+                                     "bytes_algorithmic": yb, "achieved_GBs": round(yb / (ed_ms / 1e3) / 1e9, 1),
+                                     "hbm_frac": round(yb / (ed_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+                                     "line_ms": round(eln_ms, 4),
+                                     "line_hbm_frac": round(2 * yb / (eln_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
+                                     "over_line": round(ed_ms / eln_ms, 2),
+                                     "sums_preview_ms": round(ep_ms, 4),
+                                     "points_frame0": int(esums[0, 0])}
+        del edev
     # the MxN colour-grid sensor over the same bytes as the line row (scene
     # frames), then over uniform random bytes; colours only, no preview
     out["mxn"] = {"frames": lf, "bytes_algorithmic": lf * lfb,

@@ -1,6 +1,7 @@
 // trik_hsv_batch.cpp -- Layer 2 of the C ABI: the batched device API
 // (trik_hsv_*), each entry point its argument checks and then the shared
 // enqueue path (run_sums, or the sensor's core in trik_hsv_sensors.cpp).
+#include <math.h>
 #include <string.h>
 
 #include "trik_hsv_handle.h"
@@ -325,6 +326,74 @@ extern "C" uint32_t trik_hsv_mxn_color(int32_t h_bin, int32_t s_bin, int32_t v_b
     return 0;
   }
   return mxn_color_table()[(h_bin << 4) | (s_bin << 2) | v_bin];
+}
+
+extern "C" int32_t trik_hsv_edge_batch(const TrikHsvFrameBatch* b, int32_t threshold, TrikHsvTargetSums* sums,
+                                       TrikHsvTarget* targets, uint8_t* edges, void* stream) {
+  int32_t rc = check_batch(b);
+  if (!rc) rc = check_ov7670(b, "edge-line");
+  if (rc) return rc;
+  const std::string e = edge_geometry_error(b->width, b->height, b->line_length);
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  if (threshold < 0 || threshold > 255) return fail(TRIK_IVIDTRANSCODE_EFAIL, "edge_batch: threshold must be 0..255");
+  if (b->n_frames > 0 && !sums) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (b->n_frames == 0) return 0;
+  HIP_TRY(hipMemsetAsync(sums, 0, sizeof(TrikHsvTargetSums) * (size_t)b->n_frames, s));
+  if (b->width == 0 || b->height == 0) {
+    if (targets) HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * (size_t)b->n_frames, s));
+    return 0;
+  }
+  HIP_TRY(launch_edge(edge_args(*b, threshold, sums, targets, edges), s));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_edge_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                         int32_t threshold, const TrikHsvTargetSums* sums, int32_t out_width,
+                                         int32_t out_height, int32_t out_line_length, uint8_t* previews,
+                                         int64_t preview_stride, void* stream) {
+  int32_t rc = check_handle_batch(h, b);
+  if (!rc) rc = check_ov7670(b, "edge-line");
+  if (rc) return rc;
+  const std::string e = edge_geometry_error(b->width, b->height, b->line_length);
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  if (threshold < 0 || threshold > 255)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "edge_preview: threshold must be 0..255");
+  int64_t pb = 0;
+  rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && sums, &pb);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0 || pb == 0) return 0;
+  rc = check_device(h, b, previews);
+  if (rc) return rc;
+  if (b->width == 0 || b->height == 0) {  // no pixel to write: the zero fill alone
+    for (int32_t f = 0; f < b->n_frames; ++f)
+      HIP_TRY(hipMemsetAsync(previews + (int64_t)f * (b->n_frames > 1 ? preview_stride : 0), 0, (size_t)pb, s));
+    return 0;
+  }
+  return edge_preview_core(h, *b, threshold, sums, out_width, out_height, out_line_length, previews, preview_stride,
+                           s);
+}
+
+// ESEQ:397-417 on the host, as edge_targets_kernel on the device
+extern "C" int32_t trik_hsv_edge_targets(const TrikHsvTargetSums* sums, int32_t width, int32_t height,
+                                         TrikHsvTarget* target) {
+  if (!sums || !target) return fail(TRIK_IVIDTRANSCODE_EFAIL, "edge_targets: NULL argument");
+  if (width <= 0 || height <= 0 || width > kEdgeMaxSide || height > kEdgeMaxSide)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "edge_targets: need 0 < width, height <= 2048");
+  TrikHsvTarget t = {0, 0, 0, 0};
+  const uint32_t n = (uint32_t)sums->points;
+  if (n > 0) {
+    const int32_t tx = (int32_t)((uint32_t)(int32_t)sums->sum_x / n);
+    const uint32_t radius = (uint32_t)ceilf(sqrtf((float)n / 3.1415927f));
+    t.x = (int8_t)(((tx - width / 2) * 100 * 2) / width);
+    t.y = (int8_t)(((0 - height / 2) * 100 * 2) / height);
+    t.size = (uint8_t)((uint32_t)(radius * 100 * 4) / (uint32_t)(width + height));
+  }
+  *target = t;
+  return 0;
 }
 
 extern "C" int32_t trik_hsv_jpeg_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, int32_t quality,

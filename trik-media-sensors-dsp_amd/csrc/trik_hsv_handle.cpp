@@ -201,6 +201,10 @@ int32_t setup_image_desc(TrikCvHandle* h) {
   const int row = layout == TRIK_HSV_LAYOUT_YUYV ? 2 * in_w : in_w;
   if (in_h > 0 && in_ll < row)
     return fail(TRIK_IALG_EFAIL, "CV algorithm setup failed: inputLineLength shorter than a row");
+  if (h->algo == kAlgoEdge) {  // the reference does not check: its Sobel pass assumes lineLength == width
+    const std::string e = edge_geometry_error(in_w, in_h, in_ll);
+    if (!e.empty()) return fail(TRIK_IALG_EFAIL, "CV algorithm setup failed: " + e);
+  }
   h->layout = layout;
   h->in_w = in_w; h->in_h = in_h; h->in_ll = in_ll;
   h->out_w = out_w; h->out_h = out_h; h->out_ll = out_ll;
@@ -222,7 +226,7 @@ int32_t setup_dynamic(TrikCvHandle* h, const TRIK_VIDTRANSCODE_CV_DynamicParams*
 // ---------------------------------------------------------------------------
 extern "C" TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_FXNS, TRIK_VIDTRANSCODE_CV_OV7670_FXNS,
     TRIK_VIDTRANSCODE_CV_LINE_FXNS, TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS, TRIK_VIDTRANSCODE_CV_MXN_FXNS,
-    TRIK_VIDTRANSCODE_CV_JPEG_FXNS;
+    TRIK_VIDTRANSCODE_CV_JPEG_FXNS, TRIK_VIDTRANSCODE_CV_EDGE_LINE_FXNS;
 
 static const TRIK_IALG_Fxns* table_of(int algo) {
   switch (algo) {
@@ -231,6 +235,7 @@ static const TRIK_IALG_Fxns* table_of(int algo) {
     case kAlgoWLine: return &TRIK_VIDTRANSCODE_CV_WEBCAM_LINE_FXNS.ialg;
     case kAlgoMxn: return &TRIK_VIDTRANSCODE_CV_MXN_FXNS.ialg;
     case kAlgoJpeg: return &TRIK_VIDTRANSCODE_CV_JPEG_FXNS.ialg;
+    case kAlgoEdge: return &TRIK_VIDTRANSCODE_CV_EDGE_LINE_FXNS.ialg;
     default: return &TRIK_VIDTRANSCODE_CV_FXNS.ialg;
   }
 }
@@ -256,7 +261,8 @@ static int32_t init_handle(TrikCvHandle* h, int algo, const TRIK_VIDTRANSCODE_CV
   h->algo = algo;
   // (the webcam line sensor's glue has the webcam object sensor's Params)
   h->params = params ? *params
-                     : default_params(algo == kAlgoLine || algo == kAlgoBlob || algo == kAlgoMxn || algo == kAlgoJpeg
+                     : default_params(algo == kAlgoLine || algo == kAlgoBlob || algo == kAlgoMxn || algo == kAlgoJpeg ||
+                                              algo == kAlgoEdge
                                           ? TRIK_VIDTRANSCODE_CV_VIDEO_FORMAT_YUV422P
                                           : TRIK_VIDTRANSCODE_CV_VIDEO_FORMAT_YUV422);  // WGLUE:188-191
   const int32_t rc = setup_dynamic(h, nullptr);      // WFXNS:158-163
@@ -307,6 +313,11 @@ extern "C" int32_t TRIK_VIDTRANSCODE_CV_create_mxn(const TRIK_VIDTRANSCODE_CV_Pa
 extern "C" int32_t TRIK_VIDTRANSCODE_CV_create_jpeg(const TRIK_VIDTRANSCODE_CV_Params* params,
                                                     TRIK_VIDTRANSCODE_CV_Handle* out_handle) {
   return create_handle(kAlgoJpeg, params, out_handle);
+}
+
+extern "C" int32_t TRIK_VIDTRANSCODE_CV_create_edge_line(const TRIK_VIDTRANSCODE_CV_Params* params,
+                                                         TRIK_VIDTRANSCODE_CV_Handle* out_handle) {
+  return create_handle(kAlgoEdge, params, out_handle);
 }
 
 extern "C" int32_t TRIK_VIDTRANSCODE_CV_delete(TRIK_VIDTRANSCODE_CV_Handle handle) {
@@ -440,6 +451,8 @@ TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_MXN_FXNS = {
     TRIK_IALGFXNS(TRIK_VIDTRANSCODE_CV_MXN_FXNS, ialg_init_as<kAlgoMxn>), xdais_process, xdais_control};
 TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_JPEG_FXNS = {
     TRIK_IALGFXNS(TRIK_VIDTRANSCODE_CV_JPEG_FXNS, ialg_init_as<kAlgoJpeg>), xdais_process, xdais_control};
+TRIK_IVIDTRANSCODE_Fxns TRIK_VIDTRANSCODE_CV_EDGE_LINE_FXNS = {
+    TRIK_IALGFXNS(TRIK_VIDTRANSCODE_CV_EDGE_LINE_FXNS, ialg_init_as<kAlgoEdge>), xdais_process, xdais_control};
 }
 
 extern "C" int32_t TRIK_VIDTRANSCODE_CV_alloc(const TRIK_IALG_Params* params, TRIK_IALG_Fxns** parent_fxns,

@@ -31,7 +31,10 @@
 // kAlgoJpeg: the ov7670 JPEG encoder (JPGEncoderWrapper<YUV422P, RGB565X> of
 // trik/ov7670/jpeg_encoder/include/internal/cv_jpeg_encoder_wrapper_seqpass.hpp
 // -- JWRAP -- over jpeg_encoder_reference.hpp -- JENC -- behind the same glue).
-enum Algo { kAlgoBall = 0, kAlgoLine = 1, kAlgoBlob = 2, kAlgoWLine = 3, kAlgoMxn = 4, kAlgoJpeg = 5 };
+// kAlgoEdge: the ov7670 edge-line sensor (BallDetector<YUV422P, RGB565X> of
+// trik/ov7670/edge_line_sensor/include/internal/cv_ball_detector_seqpass.hpp
+// -- ESEQ -- behind the same glue; inputLineLength must equal inputWidth).
+enum Algo { kAlgoBall = 0, kAlgoLine = 1, kAlgoBlob = 2, kAlgoWLine = 3, kAlgoMxn = 4, kAlgoJpeg = 5, kAlgoEdge = 6 };
 
 // ---------------------------------------------------------------------------
 // Handle
@@ -427,6 +430,16 @@ int32_t jpeg_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int quality, bool
 // walk reads past the planes otherwise), both sides at most 65535 (SOF0), and a
 // worst-case stream below 2^31 bytes
 std::string jpeg_geometry_error(int64_t width, int64_t height);
+
+// the edge-line sensor: "" when the geometry is one it takes (line_length ==
+// width, both sides <= kEdgeMaxSide; the reference's statics hold 320 x 240)
+std::string edge_geometry_error(int64_t width, int64_t height, int64_t line_length);
+EdgeArgs edge_args(const TrikHsvFrameBatch& b, int threshold, TrikHsvTargetSums* sums, TrikHsvTarget* targets,
+                   uint8_t* edges);
+// its preview: the thresholded map through IMG_ycbcr422pl_to_rgb565 with the
+// frame's chroma, every source pixel, then the target line (ESEQ:226-249, 405)
+int32_t edge_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int threshold, const TrikHsvTargetSums* sums,
+                          int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);
 
 }  // namespace trik_hsv
 #pragma GCC visibility pop

@@ -403,6 +403,41 @@ int launch_mxn_preview(const MxnPreviewArgs& a, hipStream_t s);
 constexpr int kMxnColors = 32 * 4 * 4;
 const uint32_t* mxn_color_table();
 
+// ov7670 edge-line sensor of N frames (trik_hsv_edge.hip), ESEQ
+// = trik/ov7670/edge_line_sensor/include/internal/cv_ball_detector_seqpass.hpp.
+// line_length == width (checked by the callers).  sums[f] = {points, sum_x, 0},
+// zeroed by the caller; each row's count and column sum wrap mod 65536
+// (ESEQ:160-161, 203-204).
+constexpr int kEdgeMaxSide = 2048;  // width and height (the ov7670 object sensor's cap)
+struct EdgeArgs {
+  const uint8_t* frames;
+  int64_t frame_stride;
+  int32_t n_frames, width, height;
+  int32_t threshold;  // 0..255 (50 in the codec, ESEQ:183)
+  TrikHsvTargetSums* sums;
+  TrikHsvTarget* targets;  // may be NULL
+  uint8_t* edges;          // optional [n][height][width]: the thresholded map
+};
+struct EdgePreviewArgs {
+  const uint8_t* frames;
+  int64_t frame_stride;
+  int32_t n_frames, width, height;
+  int32_t threshold;
+  const TrikHsvTargetSums* sums;  // [n]: the target line's column
+  int32_t out_w, out_h, out_ll;
+  uint8_t* previews;
+  int64_t preview_stride;
+  const uint32_t* wi2wo;    // [width]  (preview_maps)
+  const uint32_t* hi2ho;    // [height]
+  const int32_t* last_row;  // [out_h]
+  const int32_t* last_col;  // [out_w]
+};
+// sums (and the map when a.edges is set), then the targets when a.targets is set
+int launch_edge(const EdgeArgs& a, hipStream_t s);
+int launch_edge_targets(int n_frames, int width, int height, const TrikHsvTargetSums* sums, TrikHsvTarget* targets,
+                        hipStream_t s);
+int launch_edge_preview(const EdgePreviewArgs& a, hipStream_t s);
+
 // ov7670 JPEG encoder of N frames (trik_hsv_jpeg.hip), JENC =
 // trik/ov7670/jpeg_encoder/include/internal/jpeg_encoder_reference.hpp.  A
 // data unit (DU) is one 8x8 block of one component; a frame's DUs are ordered

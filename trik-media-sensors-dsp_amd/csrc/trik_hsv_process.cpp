@@ -165,6 +165,26 @@ int32_t process_mxn(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewOu
   return 0;
 }
 
+// BallDetector<YUV422P>::run of the edge-line sensor, ESEQ:365-420: every
+// InArgs field is ignored (the threshold is the codec's 50, ESEQ:183), the
+// detect* OutArgs are left untouched.
+int32_t process_edge(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewOut& pv,
+                     TRIK_VIDTRANSCODE_CV_OutArgsAlg& oa) {
+  constexpr int kThreshold = 50;
+  HIP_TRY(launch_edge(edge_args(b, kThreshold, h->d_sums, h->d_targets, nullptr), h->stream));
+  int32_t r = 0;
+  if (pv.bytes) {
+    r = edge_preview_core(h, b, kThreshold, h->d_sums, h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes,
+                          h->stream);
+    if (r) return r;
+  }
+  TrikHsvTarget t;
+  r = read_back(h, pv, h->d_targets, &t, 1);
+  if (r) return r;
+  set_target(oa, t);
+  return 0;
+}
+
 // JPGEncoderWrapper::run, JWRAP:52-77: the stream into the caller's output
 // buffer (`out`, `cap` bytes; NULL: no output stream, the size alone) and its
 // length into OutArgs.  A stream longer than the buffer fails the run with
@@ -241,6 +261,7 @@ int32_t run_sensor(TrikCvHandle* h, const void* frame, const PreviewOut& pv, int
     case kAlgoBlob: return process_blob(h, b, pv, ia7->alg, oa7->alg);
     case kAlgoLine: return process_line(h, b, pv, in_args->alg, oa);
     case kAlgoWLine: return process_wline(h, b, pv, in_args->alg, oa);
+    case kAlgoEdge: return process_edge(h, b, pv, oa);
     default: return process_ball(h, b, pv, in_args->alg, oa);
   }
 }

@@ -423,6 +423,51 @@ int32_t trik_hsv::mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, 
   return note_uses(h, nullptr, true, s);
 }
 
+std::string trik_hsv::edge_geometry_error(int64_t width, int64_t height, int64_t line_length) {
+  if (height > 0 && line_length != width)
+    return "the edge-line sensor takes inputLineLength == inputWidth (the Sobel pass reads the Y plane as one "
+           "linear array, ESEQ:179)";
+  if (width > kEdgeMaxSide || height > kEdgeMaxSide) return "frame too large for the edge-line sensor (2048 x 2048)";
+  return "";
+}
+
+EdgeArgs trik_hsv::edge_args(const TrikHsvFrameBatch& b, int threshold, TrikHsvTargetSums* sums,
+                             TrikHsvTarget* targets, uint8_t* edges) {
+  EdgeArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height;
+  a.threshold = threshold;
+  a.sums = sums;
+  a.targets = targets;
+  a.edges = edges;
+  return a;
+}
+
+int32_t trik_hsv::edge_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int threshold,
+                                    const TrikHsvTargetSums* sums, int ow, int oh, int oll, uint8_t* previews,
+                                    int64_t stride, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+  if (rc) return rc;
+  EdgePreviewArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height;
+  a.threshold = threshold;
+  a.sums = sums;
+  a.out_w = ow; a.out_h = oh; a.out_ll = oll;
+  a.previews = previews;
+  a.preview_stride = stride;
+  a.wi2wo = h->d_maps;
+  a.hi2ho = a.wi2wo + b.width;
+  a.last_row = reinterpret_cast<const int32_t*>(a.hi2ho + b.height);
+  a.last_col = a.last_row + oh;
+  HIP_TRY(launch_edge_preview(a, s));
+  return note_uses(h, nullptr, true, s);
+}
+
 std::string trik_hsv::jpeg_geometry_error(int64_t width, int64_t height) {
   if (height % 8 != 0)
     return "the JPEG encoder takes height % 8 == 0 (the reference's block walk reads past the planes otherwise)";

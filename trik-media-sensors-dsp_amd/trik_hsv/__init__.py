@@ -371,6 +371,25 @@ class Detector(_HotKernel):
         return previews
 
 
+    def edge_preview(self, frames, width, height, line_length, sums, threshold=50, *, out_width=None,
+                     out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
+        """Edge-line previews (uint8 [N, out_height, out_line_length], native
+        uint16 RGB565 pixels) from edge_batch's sums and the same threshold."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
+        ow = width // 2 if out_width is None else out_width
+        oh = height // 2 if out_height is None else out_height
+        oll = 2 * ow if out_line_length is None else out_line_length
+        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        rc = _lib.trik_hsv_edge_preview(self._h, C.byref(b), int(threshold), C.c_void_p(sums.data_ptr()), ow, oh,
+                                        oll, C.c_void_p(previews.data_ptr()), oh * oll,
+                                        _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_edge_preview")
+        return previews
+
+
 def line_batch(frames, width, height, line_length, val_from, val_to, *, band=None, n_frames=None,
                frame_stride=None, stream=None):
     """The ov7670 line sensor over N frames (LSEQ:376-476): sums int64 [N, 3] =
@@ -389,6 +408,37 @@ def line_batch(frames, width, height, line_length, val_from, val_to, *, band=Non
     if rc:
         raise TrikHsvError(rc, "trik_hsv_line_batch")
     return sums, targets
+
+
+def edge_batch(frames, width, height, line_length, threshold=50, *, edges=False, n_frames=None,
+               frame_stride=None, stream=None):
+    """The ov7670 edge-line sensor over N frames (ESEQ:154-205, 397-417): sums
+    int64 [N, 3] = {points, sum_x, 0} and targets int8 [N, 4] (targetX,
+    targetY, targetSize); with `edges`, also the thresholded Sobel map uint8
+    [N, height, width].  line_length must equal width."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
+    sums = torch.empty((b.n_frames, 3), dtype=torch.int64, device=frames.device)
+    targets = torch.empty((b.n_frames, 4), dtype=torch.int8, device=frames.device)
+    emap = torch.empty((b.n_frames, height, width), dtype=torch.uint8, device=frames.device) if edges else None
+    rc = _lib.trik_hsv_edge_batch(C.byref(b), int(threshold), C.c_void_p(sums.data_ptr()),
+                                  C.c_void_p(targets.data_ptr()), C.c_void_p(emap.data_ptr()) if edges else None,
+                                  _stream_ptr(stream, frames))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_edge_batch")
+    return (sums, targets, emap) if edges else (sums, targets)
+
+
+def edge_targets(points: int, sum_x: int, width: int, height: int) -> Tuple[int, int, int]:
+    """The edge-line sensor's (targetX, targetY, targetSize) of one frame's
+    sums: trik_hsv_edge_targets, host code."""
+    s = _abi.TargetSums(int(points), int(sum_x), 0)
+    t = _abi.Target()
+    rc = _lib.trik_hsv_edge_targets(C.byref(s), int(width), int(height), C.byref(t))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_edge_targets")
+    return int(t.x), int(t.y), int(t.size)
 
 
 def mxn_color(h: int, s: int, v: int) -> int:
@@ -798,3 +848,24 @@ class JpegSensor(ObjectSensor):
         if rc == IVIDTRANSCODE_EOK and out_buffer is not None:
             stream = bytes(out_buffer.reshape(-1).view("uint8")[: int(oa.alg.size)])
         return rc, oa, stream
+
+
+class EdgeLineSensor(ObjectSensor):
+    """The ov7670 edge-line sensor's codec instance (trik/ov7670/edge_line_sensor:
+    BallDetector<YUV422P, RGB565X> -- Sobel, threshold 50, column centroid --
+    behind the ov7670 object sensor's glue): the object sensor's InArgs and
+    OutArgs; every InArgs field is ignored, the detect* OutArgs stay untouched.
+    inputLineLength must equal inputWidth.  The preview is native uint16 RGB565."""
+
+    _create = "TRIK_VIDTRANSCODE_CV_create_edge_line"
+
+    def __init__(self, params: _abi.Params | None = None):
+        super().__init__(params)
+        if params is None:
+            self.params = _default_params(1, fmt_in=FORMAT_YUV422P)
+
+    def process(self, frame, out_buffer=None, hsv_range: Sequence[int] = (0, 0, 0, 0, 0, 0), auto_detect=False,
+                num_bytes=None, input_id=0):
+        """One host frame -> (rc, OutArgs); hsv_range and auto_detect only fill
+        the InArgs the sensor ignores."""
+        return super().process(frame, hsv_range, out_buffer, auto_detect, num_bytes, input_id)

@@ -209,6 +209,7 @@ PROTOTYPES = {
     "TRIK_VIDTRANSCODE_CV_create_webcam_line": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_create_mxn": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_create_jpeg": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
+    "TRIK_VIDTRANSCODE_CV_create_edge_line": ([C.POINTER(Params), C.POINTER(C.c_void_p)], i32),
     "TRIK_VIDTRANSCODE_CV_delete": ([C.c_void_p], i32),
     # InArgs / OutArgs by pointer: the webcam structs, the OV7670 ones for a
     # create_ov7670 handle, the MXN ones for a create_mxn handle or the JPEG
@@ -248,6 +249,10 @@ PROTOTYPES = {
     "trik_hsv_jpeg_batch": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, C.c_int64, C.c_int64,
                              C.c_void_p, C.c_void_p, C.c_void_p], i32),
     "trik_hsv_jpeg_header": ([i32, i32, i32, i32, C.c_void_p, i32], i32),
+    "trik_hsv_edge_batch": ([C.POINTER(FrameBatch), i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_edge_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, C.c_void_p, i32, i32, i32, C.c_void_p,
+                               C.c_int64, C.c_void_p], i32),
+    "trik_hsv_edge_targets": ([C.POINTER(TargetSums), i32, i32, C.POINTER(Target)], i32),
     "trik_hsv_synth": ([C.POINTER(FrameBatch), i32, i32, u64, C.c_void_p], i32),
     "trik_hsv_set_hot_kernel": ([C.c_void_p, i32], i32),
     "trik_hsv_last_hot_kernel": ([C.c_void_p], i32),

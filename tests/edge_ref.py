@@ -26,9 +26,9 @@ ESEQ:154-268, 365-420 builds on them they are the contract.
     the truncated scale maps (last writer in raster order wins), then the
     target line.
 
-`edge_map` and `preview` are vectorised; `edge_map_scalar` and
-`preview_scalar` are the literal loops, and tests/test_edge_cpu.py holds the
-two equal."""
+`edge_map`, `sums` and `preview` are vectorised; `edge_map_scalar`,
+`sums_scalar` and `preview_scalar` are the literal loops, and
+tests/test_edge_cpu.py holds the two equal."""
 import numpy as np
 
 COEFF = (0x2000, 0x2BDD, -0x0AC5, -0x1658, 0x3770)
@@ -52,26 +52,39 @@ def edge_map_scalar(frame, width, height, thr=50):
     return np.array(out, np.uint8).reshape(height, width)
 
 
-def sobel(frame, width, height):
-    """IMG_sobel_3x3_8 before the threshold: int32 [height * width]."""
+def hv(frame, width, height):
+    """The signed H and V of IMG_sobel_3x3_8: two int32 [height * width],
+    element i + 1 = window i, 0 where the loop never writes."""
     a = luma(frame, width, height).astype(np.int32)
     w, n = width, width * (height - 2) - 2
-    H = -a[0:n] - 2 * a[1:n + 1] - a[2:n + 2] + a[2 * w:2 * w + n] + 2 * a[2 * w + 1:2 * w + 1 + n] + \
+    H = np.zeros(width * height, np.int32)
+    V = np.zeros(width * height, np.int32)
+    H[1:n + 1] = -a[0:n] - 2 * a[1:n + 1] - a[2:n + 2] + a[2 * w:2 * w + n] + 2 * a[2 * w + 1:2 * w + 1 + n] + \
         a[2 * w + 2:2 * w + 2 + n]
-    V = -a[0:n] + a[2:n + 2] - 2 * a[w:w + n] + 2 * a[w + 2:w + 2 + n] - a[2 * w:2 * w + n] + a[2 * w + 2:2 * w + 2 + n]
-    out = np.zeros(width * height, np.int32)
-    out[1:n + 1] = np.minimum(np.abs(H) + np.abs(V), 255)
-    return out
+    V[1:n + 1] = -a[0:n] + a[2:n + 2] - 2 * a[w:w + n] + 2 * a[w + 2:w + 2 + n] - a[2 * w:2 * w + n] + \
+        a[2 * w + 2:2 * w + 2 + n]
+    return H, V
+
+
+def sobel(frame, width, height):
+    """IMG_sobel_3x3_8 before the threshold: int32 [height * width]."""
+    H, V = hv(frame, width, height)
+    return np.minimum(np.abs(H) + np.abs(V), 255)
+
+
+def threshold(o, width, height, thr=50):
+    """IMG_thr_gt2max_8 of sobel()'s output: uint8 [height, width]."""
+    return np.where(o > thr, 255, o).astype(np.uint8).reshape(height, width)
 
 
 def edge_map(frame, width, height, thr=50):
     """The thresholded map: uint8 [height, width]."""
-    o = sobel(frame, width, height)
-    return np.where(o > thr, 255, o).astype(np.uint8).reshape(height, width)
+    return threshold(sobel(frame, width, height), width, height, thr)
 
 
-def sums(emap, wrap=True):
-    """(points, sum_x) of ESEQ:189-205; wrap=False: without the uint16 wraps."""
+def sums_scalar(emap, wrap=True):
+    """(points, sum_x) of ESEQ:189-205, the literal loops; wrap=False: without
+    the uint16 wraps."""
     height, width = emap.shape
     points = sum_x = 0
     for r in range(height):
@@ -82,6 +95,18 @@ def sums(emap, wrap=True):
         points += n
         sum_x += sx
     return points, sum_x
+
+
+def sums(emap, wrap=True):
+    """sums_scalar, vectorised: the rows' counts and column sums, each cut to
+    uint16 before the rows are added."""
+    height, width = emap.shape
+    det = emap[:, 16:width - 15] == 0xFF
+    n = det.sum(axis=1, dtype=np.int64)
+    sx = (det * np.arange(16, width - 15, dtype=np.int64)).sum(axis=1)
+    if wrap:
+        n, sx = n & 0xFFFF, sx & 0xFFFF
+    return int(n.sum()), int(sx.sum())
 
 
 def _cdiv(a, b):
@@ -127,9 +152,11 @@ def scale_maps(width, height, out_w, out_h):
 
 
 def _line(out16, wi2wo, hi2ho, points, sum_x, width, height):
-    if points <= 0:
+    points &= 0xFFFFFFFF
+    if points == 0:
         return
     tx = (sum_x & 0xFFFFFFFF) // points
+    tx = tx - (1 << 32) if tx >= 1 << 31 else tx  # targetX is an int32_t (ESEQ:399)
     col = min(max(tx, 0), width - 1)
     for adj in range(100):
         for row in (height // 2 - adj, height // 2 + adj):
@@ -195,4 +222,19 @@ def single_pixel(width, height, row, col, base=100, value=255):
     fr = np.full(2 * width * height, 128, np.uint8)
     fr[:width * height] = base
     fr[row * width + col] = value
+    return fr
+
+
+def level_frame(width, height, level, chroma=128):
+    """Rows 0, 0, x, x, ... with x = level // 4 in even and level // 2 -
+    level // 4 in odd columns: s = a[c-1] + 2a[c] + a[c+1] = 2 (level // 2) on
+    the x rows, so for an even level H = +-level and V = 0, and the Sobel
+    magnitude is exactly `level` on columns 1 .. width-2 of map rows
+    0 .. height-3."""
+    fr = np.full(2 * width * height, chroma, np.uint8)
+    y = fr[:width * height].reshape(height, width)
+    y[:] = 0
+    rows = np.arange(height) % 4 >= 2
+    y[rows, 0::2] = level // 4
+    y[rows, 1::2] = level // 2 - level // 4
     return fr

@@ -1,6 +1,8 @@
 """CPU-only checks of the ov7670 edge-line sensor: the test reference itself
 (tests/edge_ref.py: its vectorised forms against the literal loops, the
-per-row uint16 wrap, the parity of the Sobel magnitude), the host-side OutArgs
+per-row uint16 wrap, the parity of the Sobel magnitude, the int32 line column),
+the inputs of the GPU sweeps (tests/edge_cases.py: that each reaches what it is
+meant to reach, stated on the reference's output), the host-side OutArgs
 (trik_hsv_edge_targets runs without a GPU), and the new exports: the symbols
 and the function table bind from plain C."""
 import ctypes as C
@@ -11,6 +13,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import edge_cases
 import edge_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,6 +45,82 @@ def test_vectorised_preview_equals_scalar_loops(geom):
     for points in (p, 0):
         want = edge_ref.preview_scalar(fr, w, h, emap, points, sx, ow, oh, oll)
         assert np.array_equal(edge_ref.preview(fr, w, h, emap, points, sx, ow, oh, oll), want), (geom, points)
+
+
+@pytest.mark.parametrize("geom", [(32, 4), (64, 8), (96, 12), (384, 4)])
+def test_vectorised_sums_equal_scalar_loops(geom):
+    w, h = geom
+    rng = np.random.default_rng(w * 1000 + h + 1)
+    frames = [rng.integers(0, 256, 2 * w * h, dtype=np.uint8), edge_ref.level_frame(w, h, 1020)]
+    for fr in frames:
+        for thr in (0, 50, 255):
+            emap = edge_ref.edge_map(fr, w, h, thr)
+            for wrap in (True, False):
+                assert edge_ref.sums(emap, wrap) == edge_ref.sums_scalar(emap, wrap), (geom, thr, wrap)
+    # the level frame detects every window pixel: at 384 columns the wrap decides its column sum
+    p, sx = edge_ref.sums(edge_ref.edge_map(frames[1], w, h))
+    assert p == (h - 2) * (w - 31)
+    assert (edge_ref.sums(edge_ref.edge_map(frames[1], w, h), wrap=False)[1] != sx) == (w >= 384)
+
+
+def test_preview_line_column_is_an_int32():
+    """targetX is an int32_t (ESEQ:399): a quotient with bit 31 set is negative
+    and clamps to column 0, in the loops and in the vectorised form alike."""
+    w, h = 64, 8
+    rng = np.random.default_rng(9)
+    fr = rng.integers(0, 256, 2 * w * h, dtype=np.uint8)
+    emap = edge_ref.edge_map(fr, w, h)
+    cases = [(1, -1, 0), (1, 1 << 31, 0), (1, (1 << 32) - 5, 0), (2, -1, w - 1), (3, (1 << 32) - 1, w - 1),
+             (1, 20, 20), (1, w + 500, w - 1), (1 << 32, 5, None), (0, 5, None)]
+    for points, sum_x, col in cases:
+        want = edge_ref.preview_scalar(fr, w, h, emap, points, sum_x, w, h, 2 * w)
+        assert np.array_equal(edge_ref.preview(fr, w, h, emap, points, sum_x, w, h, 2 * w), want), (points, sum_x)
+        px = want.view("<u2")
+        line = (px == edge_ref.LINE_PIXEL).all(axis=0)  # H = 8: the line spans every row
+        assert np.flatnonzero(line).tolist() == ([] if col is None else [col]), (points, sum_x)
+
+
+@pytest.mark.parametrize("level", [0, 2, 6, 50, 52, 254, 256, 300, 1020])
+def test_level_frame_has_one_magnitude(level):
+    for w, h in ((64, 8), (2048, 68)):
+        H, V = edge_ref.hv(edge_ref.level_frame(w, h, level), w, h)
+        H, V = H.reshape(h, w)[:h - 2, 1:w - 1], V.reshape(h, w)[:h - 2, 1:w - 1]
+        assert (np.abs(H) == level).all() and not V.any()
+        assert (H[0::4] == level).all() and (H[2::4] == -level).all()
+        o = edge_ref.sobel(edge_ref.level_frame(w, h, level), w, h).reshape(h, w)
+        assert (o[:h - 2, 1:w - 1] == min(level, 255)).all() and not o[h - 2:].any()
+
+
+def test_sweep_inputs_cover_what_they_claim():
+    """The inputs of the GPU threshold sweep, on the reference: the noise
+    ladder holds every even magnitude and one past the cap in each sign
+    quadrant, the two axis frames hold them with H = 0 and with V = 0, and the
+    last-row frame detects in map row H-3 alone."""
+    edge_cases.check_ladder(edge_cases.noise_ladder())
+    edge_cases.check_axis(edge_cases.h0_frame(), *edge_cases.H0_GEOM, "h0")
+    edge_cases.check_axis(edge_cases.v0_frame(), *edge_cases.V0_GEOM, "v0")
+    for w in (64, 320):
+        for h in (20, 36, 292, 308):
+            edge_cases.check_last_row(edge_cases.last_row_frame(w, h), w, h)
+    # a level frame at threshold t: all of the window or nothing
+    w, h = 64, 8
+    for level in edge_cases.SWEEP_LEVELS:
+        o = edge_ref.sobel(edge_ref.level_frame(w, h, level), w, h)
+        for thr in range(256):
+            p, _ = edge_ref.sums(edge_ref.threshold(o, w, h, thr))
+            assert p == ((h - 2) * (w - 31) if level > thr or level >= 255 else 0), (level, thr)
+
+
+def test_preview_inputs_hold_every_luma_with_every_chroma():
+    w, h = edge_cases.PREVIEW_GEOM
+    chroma = edge_cases.preview_chroma(w, h)
+    seen = np.zeros(1 << 24, bool)
+    for level in edge_cases.PREVIEW_LEVELS:
+        fr = edge_cases.preview_frame(level, chroma)
+        edge_cases.preview_triples(fr, edge_ref.edge_map(fr, w, h, 255), seen)
+    lumas = sorted(set(np.flatnonzero(seen) >> 16))
+    assert lumas == list(range(0, 256, 2)) + [255]
+    assert int(seen.sum()) == 129 * 65536
 
 
 def test_row_sums_wrap_at_384_columns():

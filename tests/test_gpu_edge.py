@@ -4,12 +4,15 @@ trik/ov7670/edge_line_sensor/include/internal/cv_ball_detector_seqpass.hpp):
 sums, targets, the thresholded map and the preview bytes, bit-exact, through
 edge_batch / Detector.edge_preview (trik_hsv_edge_batch / trik_hsv_edge_preview),
 EdgeLineSensor.process (TRIK_VIDTRANSCODE_CV_create_edge_line) and the exported
-XDAIS function table."""
+XDAIS function table.  Every lane layout and row segmentation of the fast
+kernel, every threshold and every colour of the preview run on the inputs of
+tests/edge_cases.py, whose coverage is asserted on the reference's output."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import edge_cases
 import edge_ref
 from gpu_util import LAYOUT_OV7670
 
@@ -87,10 +90,10 @@ GEOMS = [(32, 4), (64, 8), (96, 12), (352, 8), (384, 4), (640, 8), (320, 240), (
          (1056, 4), (2048, 4)]
 
 
-@pytest.mark.parametrize("geom", GEOMS)
-def test_edge_batch_vs_reference(hsv, oracle_mod, geom):
-    w, h = geom
-    frames = make_frames(oracle_mod, w, h)
+def check_frames(hsv, frames, w, h):
+    """Sums, targets and the map of every frame, the fast and the generic
+    kernel, against the reference.  `frames` begins with make_frames()."""
+    geom = (w, h)
     refs = [ref_run(name, fr, w, h) for name, fr in frames]
     assert refs[5][1][0] == (h - 2) * (w - 31)  # the steps: every window pixel of every live row
     for i in (0, 5):  # from 384 columns the per-row uint16 wrap decides the uniform and the steps frames' sums
@@ -113,6 +116,135 @@ def test_edge_batch_vs_reference(hsv, oracle_mod, geom):
         assert flat[0] == 0 and flat[w * (h - 2) - 1] == 0 and not emap[i][h - 2:].any()
     # the wrap columns carry values (they mix two rows): the comparison above is not of zeros
     assert refs[0][0][:h - 2, 0].any() and refs[0][0][:h - 2, -1].any()
+
+
+@pytest.mark.parametrize("geom", GEOMS)
+def test_edge_batch_vs_reference(hsv, oracle_mod, geom):
+    w, h = geom
+    check_frames(hsv, make_frames(oracle_mod, w, h), w, h)
+
+
+# (width, dwords per lane, lane group): the classes of the fast kernel's lane
+# layout that GEOMS leaves out.  Full groups (a row takes every lane of its
+# group, so the column halos of its end lanes come from the neighbouring
+# group or wrap inside the wave): 128, 256, 512, 1280; partial groups: 480
+# (60 of 64 lanes), 544 and 992 (34 and 62 of 64), 1120 (56 of 64), 2016 (63
+# of 64).  GEOMS holds the others: 32..96 (2, 16), 160 (2, 32), 352 and 384
+# (2, 64), 320 (5, 16), 640 (5, 32), 1024 (4, 64), 1056 and 2048 (8, 64).
+LAYOUTS = [(128, 2, 16), (256, 2, 32), (480, 2, 64), (512, 2, 64), (544, 4, 64), (992, 4, 64), (1120, 5, 64),
+           (1280, 5, 64), (2016, 8, 64)]
+
+
+@pytest.mark.parametrize("layout", LAYOUTS, ids=lambda v: "w%d-q%d-g%d" % v)
+def test_edge_every_lane_layout(hsv, oracle_mod, layout):
+    """Seven frames of H = 8 (one row segment each): no multiple of the 4 or 2
+    groups a wave holds, so a wave's last live group sits beside an idle group
+    and every other one beside another frame's."""
+    w, q, group = layout
+    assert w % (4 * q) == 0 and w // (4 * q) <= group and (group == 16 or w // (4 * q) > group // 2)
+    h = 8
+    frames = make_frames(oracle_mod, w, h) + [("uniform2", oracle_mod.synth(1, w, h, w, LAYOUT_OV7670, 0, 0x0DD5))]
+    assert group == 64 or len(frames) % (64 // group)
+    check_frames(hsv, frames, w, h)
+
+
+HEIGHT_FRAMES = (0, 1, 2, 5)  # of make_frames: uniform, scene, binary, steps
+
+
+# h - 2 output rows in segments of at most (h - 2) / 16: 20 is the last height
+# with one segment (18 rows), 36 the first with two (17 + 17); 292 gives 18
+# segments of 17 rows whose last holds one row; 308 gives 18 segments of 17
+# rows where 19 are allowed.  64 columns: 2 dwords per lane, 320: 5.
+@pytest.mark.parametrize("w", [64, 320])
+@pytest.mark.parametrize("h", [20, 36, 292, 308])
+def test_edge_heights(hsv, oracle_mod, w, h):
+    all_frames = make_frames(oracle_mod, w, h)
+    frames = [all_frames[i] for i in HEIGHT_FRAMES] + [("lastrow", edge_cases.last_row_frame(w, h))]
+    edge_cases.check_last_row(frames[-1][1], w, h)  # points > 0, all of them in map row h - 3
+    refs = [ref_run(name, fr, w, h) for name, fr in frames]
+    assert refs[3][1][0] == (h - 2) * (w - 31) and refs[2][1][0] > 0
+    dev = upload(frames)
+    sums, targets = hsv.edge_batch(dev, w, h, w)
+    sums_m, targets_m, emap = hsv.edge_batch(dev, w, h, w, edges=True)
+    sums, targets, sums_m, targets_m, emap = (t.cpu().numpy() for t in (sums, targets, sums_m, targets_m, emap))
+    for i, (name, _) in enumerate(frames):
+        want_map, (p, sx), tg = refs[i]
+        assert sums[i].tolist() == [p, sx, 0], (w, h, name, "fast")
+        assert sums_m[i].tolist() == [p, sx, 0], (w, h, name, "generic")
+        assert targets[i, :3].tolist() == [tg[0], tg[1], tg[2] - 256 * (tg[2] > 127)], (w, h, name)
+        assert np.array_equal(targets_m[i], targets[i])
+        assert np.array_equal(emap[i], want_map), (w, h, name)
+
+
+# (frames, width, height): 512 frames of 64 x 2048 take 64 row segments of 32
+# rows (the last of 30) where the height allows 127; 32768 frames of 64 x 36
+# take one segment where the height allows two.  Smaller batches stay at the
+# height's cap, as every other test here does.
+@pytest.mark.parametrize("shape", [(512, 64, 2048), (32768, 64, 36)])
+def test_edge_segments_follow_the_batch(hsv, oracle_mod, shape):
+    """Frame i = distinct[i % 7]: every frame's sums and targets, from both kernels."""
+    import torch
+
+    n, w, h = shape
+    frames = make_frames(oracle_mod, w, h) + [("lastrow", edge_cases.last_row_frame(w, h))]
+    refs = [ref_run(name, fr, w, h) for name, fr in frames]
+    assert all(r[1][0] > 0 for r in refs[2:]) and len({r[1] for r in refs}) == 7  # seven different results
+    idx = np.arange(n) % 7
+    want_sums = np.array([[r[1][0], r[1][1], 0] for r in refs], np.int64)[idx]
+    want_tg = np.array([[r[2][0], r[2][1], r[2][2] - 256 * (r[2][2] > 127)] for r in refs], np.int8)[idx]
+    dev = upload(frames).reshape(7, 2 * w * h)[torch.from_numpy(idx).cuda()].reshape(-1)
+    assert dev.numel() == n * 2 * w * h
+    sums, targets = hsv.edge_batch(dev, w, h, w)
+    assert np.array_equal(sums.cpu().numpy(), want_sums)
+    assert np.array_equal(targets.cpu().numpy()[:, :3], want_tg)
+    sums_m, targets_m, emap = hsv.edge_batch(dev, w, h, w, edges=True)
+    assert np.array_equal(sums_m.cpu().numpy(), want_sums)
+    assert torch.equal(targets_m, targets)
+    for i in (0, 1, 2, 3, 4, 5, 6, n - 1):
+        assert np.array_equal(emap[i].cpu().numpy(), refs[i % 7][0]), (shape, i)
+
+
+def sweep_inputs():
+    """name -> (frames, width, height) of the threshold sweep."""
+    w, h = 64, 8
+    return {"levels": ([edge_ref.level_frame(w, h, lv) for lv in edge_cases.SWEEP_LEVELS], w, h),
+            "ladder": ([edge_cases.noise_ladder()],) + edge_cases.LADDER_GEOM,
+            "h0": ([edge_cases.h0_frame()],) + edge_cases.H0_GEOM,
+            "v0": ([edge_cases.v0_frame()],) + edge_cases.V0_GEOM}
+
+
+@pytest.mark.parametrize("name", ["levels", "ladder", "h0", "v0"])
+def test_edge_every_threshold(hsv, name):
+    """Thresholds 0 .. 255, both kernels, sums against the reference.  The
+    inputs put every even magnitude 2 .. 254 and one past 255 next to every
+    threshold: as a whole window (the level frames: all of it or nothing is
+    detected), in each sign quadrant of (H, V) (the ladder) and on the axes
+    H = 0 and V = 0."""
+    import torch
+
+    frames, w, h = sweep_inputs()[name]
+    if name == "ladder":
+        edge_cases.check_ladder(frames[0])
+    elif name != "levels":
+        edge_cases.check_axis(frames[0], w, h, name)
+    sobels = [edge_ref.sobel(fr, w, h) for fr in frames]
+    want = np.array([[edge_ref.sums(edge_ref.threshold(o, w, h, thr)) + (0,) for o in sobels] for thr in range(256)])
+    if name == "levels":
+        full = (h - 2) * (w - 31)
+        for j, level in enumerate(edge_cases.SWEEP_LEVELS):
+            for thr in range(256):
+                assert want[thr, j, 0] == (full if level > thr or level >= 255 else 0), (level, thr)
+    else:
+        assert len(set(want[0::2, 0, 0].tolist())) == 128  # every even threshold selects another set
+    # what the reference implies: fewer points as the threshold grows, magnitudes are even, 255 = 254
+    assert (np.diff(want[:, :, 0], axis=0) <= 0).all()
+    assert np.array_equal(want[0:254:2], want[1:254:2]) and np.array_equal(want[254], want[255])
+    dev = torch.from_numpy(np.concatenate(frames)).cuda()
+    fast = torch.stack([hsv.edge_batch(dev, w, h, w, thr)[0] for thr in range(256)]).cpu().numpy()
+    generic = torch.stack([hsv.edge_batch(dev, w, h, w, thr, edges=True)[0] for thr in range(256)]).cpu().numpy()
+    for thr in range(256):
+        assert np.array_equal(fast[thr], want[thr]), (name, thr, "fast")
+        assert np.array_equal(generic[thr], want[thr]), (name, thr, "generic")
 
 
 def test_edge_thresholds(hsv):
@@ -228,6 +360,71 @@ def test_edge_preview_vs_reference(hsv, det, oracle_mod, geom):
             assert (px[rows, col] == edge_ref.LINE_PIXEL).all()
     if (ow, oh) == (2 * w, 2 * h):  # odd output rows and columns are never written
         assert not pv[:, 1::2].any() and not pv[:, :, 2::4].any() and not pv[:, :, 3::4].any()
+
+
+@pytest.mark.parametrize("thr", [0, 49, 255])
+def test_edge_preview_thresholds(hsv, det, oracle_mod, thr):
+    """The TRIK default geometry at other thresholds than 50: the luma of the
+    conversion is the map at that threshold."""
+    w, h, ow, oh, oll = PREVIEWS[2]
+    frames = make_frames(oracle_mod, w, h)[:4]
+    dev = upload(frames)
+    sums, _ = hsv.edge_batch(dev, w, h, w, thr)
+    pv = det.edge_preview(dev, w, h, w, sums, thr, out_width=ow, out_height=oh, out_line_length=oll).cpu().numpy()
+    lumas = set()
+    for i, (name, fr) in enumerate(frames):
+        emap, (p, sx), _ = ref_run(name, fr, w, h, thr)
+        assert sums[i].tolist() == [p, sx, 0]
+        assert np.array_equal(pv[i], edge_ref.preview(fr, w, h, emap, p, sx, ow, oh, oll)), (thr, name)
+        lumas |= set(np.unique(emap).tolist())
+    assert lumas <= set(range(0, min(thr, 254) + 1, 2)) | {255} and {0, 255} <= lumas
+    assert thr == 0 or max(lumas - {255}) in (thr - 1, 254)  # up to the threshold, not up to 50
+
+
+def test_edge_preview_every_colour(hsv, det):
+    """129 level frames at threshold 255, 1:1: the map holds 0, 2, .., 254 and
+    255, and the chroma plane every (cb, cr) pair beside each of them, so the
+    conversion sees every triple it can be given."""
+    import torch
+
+    w, h = edge_cases.PREVIEW_GEOM
+    chroma = edge_cases.preview_chroma(w, h)
+    frames = [edge_cases.preview_frame(level, chroma) for level in edge_cases.PREVIEW_LEVELS]
+    refs = [edge_ref.run(fr, w, h, 255) for fr in frames]
+    seen = np.zeros(1 << 24, bool)
+    for fr, (emap, _, _) in zip(frames, refs):
+        edge_cases.preview_triples(fr, emap, seen)
+    assert int(seen.sum()) == 129 * 65536
+    dev = torch.from_numpy(np.concatenate(frames)).cuda()
+    sums, _ = hsv.edge_batch(dev, w, h, w, 255)
+    want_sums = np.array([[p, sx, 0] for _, (p, sx), _ in refs], np.int64)
+    assert np.array_equal(sums.cpu().numpy(), want_sums) and want_sums[-1, 0] == (h - 2) * (w - 31)
+    pv = det.edge_preview(dev, w, h, w, torch.from_numpy(want_sums).cuda(), 255, out_width=w, out_height=h,
+                          out_line_length=2 * w).cpu().numpy()
+    for i, (fr, (emap, (p, sx), _)) in enumerate(zip(frames, refs)):
+        want = edge_ref.preview(fr, w, h, emap, p, sx, w, h, 2 * w)
+        assert np.array_equal(pv[i], want), edge_cases.PREVIEW_LEVELS[i]
+
+
+def test_edge_preview_takes_the_callers_sums(hsv, det, oracle_mod):
+    """The line column is int32(uint32(int32(sum_x)) / uint32(points)) clamped
+    to 0 .. w-1, whatever sums the caller passes."""
+    import torch
+
+    w, h = 64, 8
+    fr = oracle_mod.synth(1, w, h, w, LAYOUT_OV7670, 1, 0x7A1C, first_frame=3)
+    # (points, sum_x, the line's column): in range, the upper clamp, a negative int32 (the lower clamp), no points
+    cases = [(1, 0, 0), (1, w - 1, w - 1), (1, w + 500, w - 1), (2, 2**31 - 1, w - 1), (1, -1, 0),
+             (3, 2**32 - 1, w - 1), (0, 5, None)]
+    dev = torch.from_numpy(np.tile(fr, len(cases))).cuda()
+    sums = torch.tensor([[p, sx, 0] for p, sx, _ in cases], dtype=torch.int64).cuda()
+    pv = det.edge_preview(dev, w, h, w, sums, out_width=w, out_height=h, out_line_length=2 * w).cpu().numpy()
+    emap = edge_ref.edge_map(fr, w, h)
+    for i, (p, sx, col) in enumerate(cases):
+        want = edge_ref.preview(fr, w, h, emap, p, sx, w, h, 2 * w)
+        assert np.array_equal(pv[i], want), (p, sx)
+        line = (pv[i].copy().view("<u2") == edge_ref.LINE_PIXEL).all(axis=0)  # H = 8: the line spans every row
+        assert np.flatnonzero(line).tolist() == ([] if col is None else [col]), (p, sx)
 
 
 def sensor(hsv, w, h, ow, oh, oll, streams=1):

@@ -21,8 +21,9 @@
 //    shape costs only the pixels in its window.  The exception code
 //    kChromaExc flags both pixels of the word.
 //  * The hot loop per YUYV word: one v_perm for c, three LDS reads (run
-//    descriptor, block word, the byte-spread mask pair), seven compares
-//    (exception code; Y0/Y1 < b1, <= b2, >= the block's cut) and four
+//    descriptor, block word, the byte-spread mask pair), one packed subtract
+//    of the block's cut from both Y (the stored b1, b2 are relative to it),
+//    five compares (exception code; Y0/Y1 - cut < b1, <= b2) and four
 //    selects; the flags are SALU operations on the compare masks.
 //    Accumulation is the stripe kernel's (byte-packed per-lane counters,
 //    lanes own chunk columns and walk rows).
@@ -73,14 +74,14 @@ constexpr int kRecCap = 70;
 // LDS image of the chroma kernel (dynamic LDS from address 0).  The block
 // masks and the mask-pair table sit below 64 KiB so their reads take an
 // immediate DS offset; the run descriptors follow.
-constexpr uint32_t kLdsBlocks = 0;                    // u16 [4096]  the 16-chroma block's pair offset | cut << 8
+constexpr uint32_t kLdsBlocks = 0;                    // u16 [4096]  the 16-chroma block's cut | pair offset << 8
 constexpr uint32_t kLdsPairs = 8192;                  // u32 [kChromaPalette][2] byte-spread (M1, M2) of the palette
 constexpr uint32_t kLdsLut43 = kLdsPairs + 8 * kChromaPalette;  // u16 [256]   s_mult43_div (WSEQ:389-407)
 constexpr uint32_t kLdsLut255 = kLdsLut43 + 512;      // u16 [256]   s_mult255_div
 constexpr uint32_t kLdsHue = kLdsLut255 + 512;        // u8  [256]   hue test per H (bit t = range t)
 constexpr uint32_t kLdsSat = kLdsHue + 256;           // u8  [256]   saturation test per S
 constexpr uint32_t kLdsVal = kLdsSat + 256;           // u8  [256]   value test per V
-constexpr uint32_t kLdsRuns = kLdsVal + 256;          // u16 [65536] b1 | b2 << 8 per chroma
+constexpr uint32_t kLdsRuns = kLdsVal + 256;          // u16 [65536] b1 | b2 << 8 per chroma, relative to the cut
 constexpr uint32_t kLdsQueues = kLdsRuns + 131072;    // blob kernel: per wave kQueueCap x {word, pos}
 static_assert(kLdsBlocks + 8192 <= kLdsPairs, "LDS layout");
 // hot kernel records: per wave kRecCap x 16 B of words, then all waves' meta
@@ -132,23 +133,27 @@ __device__ __forceinline__ void st64(uint32_t a, uint32_t x, uint32_t y) {
   *(lds64_t)(uintptr_t)a = v;
 }
 
+// The packed subtract takes the block's cut A (the block word's low byte) from
+// both halves of the word: byte 0 of t is (Y0 - A) mod 256 and byte 2 is
+// (Y1 - A) mod 256 (the borrow and the palette byte end in the U and V bytes,
+// which nothing reads).  The exception compare sits between it and the first
+// compare that reads t.
 #define TRIK_SELECT2_CMPS                                                                       \
+  "v_pk_sub_u16 %[t], %[w], %[a] op_sel_hi:[1,0]\n\t"                                           \
   "v_cmp_eq_u32_e64 %[x], %[k], %[d]\n\t"                                                       \
-  "v_cmp_gt_u32_sdwa %[lt0], %[d], %[w] src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"                    \
-  "v_cmp_gt_u32_sdwa %[lt1], %[d], %[w] src0_sel:BYTE_0 src1_sel:BYTE_2\n\t"                    \
-  "v_cmp_ge_u32_sdwa %[le0], %[d], %[w] src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"                    \
-  "v_cmp_ge_u32_sdwa %[le1], %[d], %[w] src0_sel:BYTE_1 src1_sel:BYTE_2\n\t"                    \
-  "v_cmp_le_u32_sdwa %[ge0], %[a], %[w] src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"                    \
-  "v_cmp_le_u32_sdwa %[ge1], %[a], %[w] src0_sel:BYTE_1 src1_sel:BYTE_2"
+  "v_cmp_gt_u32_sdwa %[lt0], %[d], %[t] src0_sel:BYTE_0 src1_sel:BYTE_0\n\t"                    \
+  "v_cmp_gt_u32_sdwa %[lt1], %[d], %[t] src0_sel:BYTE_0 src1_sel:BYTE_2\n\t"                    \
+  "v_cmp_ge_u32_sdwa %[le0], %[d], %[t] src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"                    \
+  "v_cmp_ge_u32_sdwa %[le1], %[d], %[t] src0_sel:BYTE_1 src1_sel:BYTE_2"
 // The selects; q0 / q1 per pixel (MASKS) or only their union (the word is
 // flagged: one SALU op fewer per word).
 template <bool PER_PIXEL>
 __device__ __forceinline__ void select2_impl(uint32_t w, uint32_t d, uint32_t bw, uint32_t m1, uint32_t m2, uint64_t vm,
                                              uint32_t& e0, uint32_t& e1, uint64_t& q0, uint64_t& q1) {
-  uint64_t x, lt0, lt1, le0, le1, ge0, ge1;
+  uint64_t x, lt0, lt1, le0, le1;
+  uint32_t t;
   asm volatile(TRIK_SELECT2_CMPS
-               : [x] "=&s"(x), [lt0] "=&s"(lt0), [lt1] "=&s"(lt1), [le0] "=&s"(le0), [le1] "=&s"(le1),
-                 [ge0] "=&s"(ge0), [ge1] "=&s"(ge1)
+               : [t] "=&v"(t), [x] "=&s"(x), [lt0] "=&s"(lt0), [lt1] "=&s"(lt1), [le0] "=&s"(le0), [le1] "=&s"(le1)
                : [w] "v"(w), [d] "v"(d), [a] "v"(bw), [k] "s"(kChromaExc));
   if (PER_PIXEL) {
     q0 = (x | (lt0 & ~le0)) & vm;
@@ -157,7 +162,7 @@ __device__ __forceinline__ void select2_impl(uint32_t w, uint32_t d, uint32_t bw
     q0 = (x | (lt0 & ~le0) | (lt1 & ~le1)) & vm;
     q1 = 0;
   }
-  const uint64_t k0 = le0 & ge0 & ~x & vm, k1 = le1 & ge1 & ~x & vm;
+  const uint64_t k0 = le0 & ~x & vm, k1 = le1 & ~x & vm;
   asm volatile(
       "v_cndmask_b32_e64 %[e0], %[m2], %[m1], %[lt0]\n\t"
       "v_cndmask_b32_e64 %[e1], %[m2], %[m1], %[lt1]\n\t"
@@ -167,14 +172,16 @@ __device__ __forceinline__ void select2_impl(uint32_t w, uint32_t d, uint32_t bw
       : [m1] "v"(m1), [m2] "v"(m2), [lt0] "s"(lt0), [lt1] "s"(lt1), [k0] "s"(k0), [k1] "s"(k1));
 }
 // The fast-path masks of the two pixels of YUYV word w under run descriptor
-// d = b1 | b2 << 8, block word bw (cut A in its byte 1) and mask pair (m1,
-// m2): with lt = Y < b1, le = Y <= b2, ge = Y >= A, e = le && ge ? (lt ? m1 :
-// m2) : 0.  Byte operands straight from w, d and bw by SDWA compares; the
-// selects follow all compares (the VALU-writes-SGPR -> v_cndmask distance
-// needs no nops).  q0 / q1 (wave masks, SALU) flag the pixels the exact path
-// resolves: a window pixel (lt and not le, where the select gives 0; windows
-// lie above the cut) or any pixel of an exception-code word (le is cleared,
-// so the select gives 0 as well).  vm masks lanes without a valid row.
+// d = b1 | b2 << 8 (both relative to the block's cut), block word bw (cut A
+// in its byte 0) and mask pair (m1, m2): with t = (Y - A) mod 256, lt = t < b1,
+// le = t <= b2, e = le ? (lt ? m1 : m2) : 0.  A pixel below the cut wraps to
+// t >= 256 - A, above every b1 and b2 of the block (<= 255 - A): neither lt
+// nor le, so it gets 0 and no flag.  Byte operands straight from t and d by
+// SDWA compares; the selects follow all compares (the VALU-writes-SGPR ->
+// v_cndmask distance needs no nops).  q0 / q1 (wave masks, SALU) flag the
+// pixels the exact path resolves: a window pixel (lt and not le, where the
+// select gives 0) or any pixel of an exception-code word (le is cleared, so
+// the select gives 0 as well).  vm masks lanes without a valid row.
 __device__ __forceinline__ void select2(uint32_t w, uint32_t d, uint32_t bw, uint32_t m1, uint32_t m2, uint64_t vm,
                                         uint32_t& e0, uint32_t& e1, uint64_t& q0, uint64_t& q1) {
   select2_impl<true>(w, d, bw, m1, m2, vm, e0, e1, q0, q1);
@@ -480,6 +487,21 @@ __device__ __forceinline__ uint32_t chroma_desc_cut(uint32_t sf, uint32_t sd, ui
   return chroma_desc(f == A ? sd : sf, k & 15u, k >> 4);
 }
 
+// The stored form of descriptor d in a block with cut A: both thresholds
+// relative to A (the hot kernel compares them with (Y - A) mod 256).  b1 < A
+// (a profile that starts at A with M2: b1 = 0) clamps to 0; b2 >= A holds for
+// every descriptor chroma_desc_cut makes but one: the all-zero form 255 |
+// 254 << 8 under A = 255, whose relative form is 1 | 0 << 8 (M1 = 0 at Y = 255,
+// 0 below the cut).  The exception code stays absolute: a relative descriptor
+// has b1 <= 255 - A, so it can equal the code only with A = 0, where nothing
+// changes.
+__device__ __forceinline__ uint32_t chroma_desc_rel(uint32_t d, uint32_t M1, uint32_t A) {
+  if (d == kChromaExc || A == 0u) return d;
+  const uint32_t b1 = d & 255u, b2 = d >> 8;
+  if (b2 < A) return M1 == 0u && b1 <= A ? (256u - A) | ((255u - A) << 8) : kChromaExc;
+  return (b1 > A ? b1 - A : 0u) | ((b2 - A) << 8);
+}
+
 // One wave per 16-chroma block b = (V << 4) | (U >> 4), 16 blocks per
 // workgroup: the candidate mask pairs k = M1 | M2 << 4 and cuts A (0, or the
 // first nonzero Y of one of the block's chromas) are listed in the wave's LDS
@@ -492,8 +514,9 @@ __device__ __forceinline__ uint32_t chroma_desc_cut(uint32_t sf, uint32_t sd, ui
 // (up to) kChromaPalette most used pairs (ties: the smaller k), palette_of[k]
 // = 8 * slot or 0xFF, with the byte-spread pair of each slot.  Then the
 // palette's pairs only (the same choice when the unrestricted pair made the
-// palette, which is nearly always), the block word (the pair's palette offset
-// | the cut << 8), the run descriptors, and the blocks' expected exact-path
+// palette, which is nearly always), the block word (the cut | the pair's
+// palette offset << 8), the run descriptors relative to the cut
+// (chroma_desc_rel), and the blocks' expected exact-path
 // words added into flagged_cost (one atomic per workgroup).
 constexpr int kBlocksPerGroup = 16;
 template <bool PALETTE>
@@ -596,9 +619,11 @@ __global__ __launch_bounds__(1024) void chroma_block_kernel(ChromaTables* ct) {
     return;
   }
   const uint32_t bk = (uint32_t)(best >> 9) & 255u, bA = (uint32_t)best & 511u;
-  if (lane < 16) ct->runs[c0 + lane] = (uint16_t)chroma_desc_cut(sf[wv][lane], sd[wv][lane], fz[wv][lane], bk, bA);
+  if (lane < 16)
+    ct->runs[c0 + lane] = (uint16_t)chroma_desc_rel(
+        chroma_desc_cut(sf[wv][lane], sd[wv][lane], fz[wv][lane], bk, bA), bk & 15u, bA);
   if (lane == 0) {
-    ct->blocks[b] = (uint16_t)(pal_of[bk] | (bA << 8));
+    ct->blocks[b] = (uint16_t)(bA | ((uint32_t)pal_of[bk] << 8));
     ct->block_cost[b] = (uint32_t)(best >> 17);
     part[wv] = best >> 17;
   }
@@ -869,8 +894,10 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
         const uint32_t i = 3u - (uint32_t)__builtin_ctz(fl);
         const uint32_t w = *(lds32_t)(uintptr_t)(rec + 4u * i);  // the record's first flagged word
         const uint32_t x = ((meta >> 4) & 0xFFFu) * 8u + 2u * i, yr = meta >> 16;
-        const uint32_t d = ld16(kLdsRuns + 2u * chroma_of(w));
-        const uint32_t lo = d & 0xFFu, hi = d >> 8, Y0 = w & 0xFFu, Y1 = (w >> 16) & 0xFFu;
+        const uint32_t c = chroma_of(w);
+        const uint32_t d = ld16(kLdsRuns + 2u * c), A = ld8(kLdsBlocks + 2u * (c >> 4));
+        // (as select2: the descriptor is relative to the block's cut)
+        const uint32_t lo = d & 0xFFu, hi = d >> 8, Y0 = (w - A) & 0xFFu, Y1 = ((w >> 16) - A) & 0xFFu;
         const bool xw = d == kChromaExc;
         const bool f0 = xw | ((Y0 < lo) & (Y0 > hi)), f1 = xw | ((Y1 < lo) & (Y1 > hi));
         const uint32_t m0 = f0 ? exact_mask<0>(w) : 0u;
@@ -934,6 +961,11 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
     const uint8_t* tbase = a.frames + (int64_t)f * a.frame_stride + (int64_t)r0 * a.line_length;
     auto run = [&](auto full_c) {
       constexpr bool FULL = decltype(full_c)::value;
+      // the two pieces' meta words without their flag bits (bits 0-3 are 0),
+      // shifted right by 4: two running registers, a step's rows further on
+      // at every step
+      uint32_t fa_run = (meta_x | ((uint32_t)ro << 16)) >> 4, fb_run = fa_run + (meta_b >> 4);
+      const uint32_t row_step = (uint32_t)g.rstep << 12;
       // One step: the chunk's 8 words.  All LDS lookups are issued before
       // any record write (the queue shares LDS, so the compiler keeps the
       // order), then the selects, then the two pieces' records.
@@ -950,9 +982,9 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
 #pragma unroll
         for (int i = 0; i < CW; ++i) {
           d[i] = ld16(kLdsRuns + (c[i] >> 7));
-          // the block word: the pair's palette offset | the cut << 8
+          // the block word: the cut | the pair's palette offset << 8
           cut[i] = ld16(kLdsBlocks + ((c[i] >> 11) & 0x1FFEu));
-          pr[i] = cut[i] & 0xFFu;
+          pr[i] = cut[i] >> 8;
         }
 #pragma unroll
         for (int i = 0; i < CW; ++i) mm[i] = ld64(kLdsPairs + pr[i]);
@@ -968,8 +1000,9 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
         // at once (held for the appends, the eight masks pushed the unit's
         // SGPRs into spills)
         uint64_t ma = 0, mb = 0;
-        const uint32_t meta_a = meta_x | ((uint32_t)(ro + s * g.rstep) << 16);
-        uint32_t fa = meta_a >> 4, fb = (meta_a + meta_b) >> 4;  // (flag bits 0-3 of the meta words are 0)
+        uint32_t fa = fa_run, fb = fb_run;
+        fa_run += row_step;  // the next step's rows (the steps come in order)
+        fb_run += row_step;
 #pragma unroll
         for (int i = 0; i < CW; ++i) {
           uint64_t q0 = 0, q1 = 0, bal;
@@ -1216,8 +1249,9 @@ __global__ __launch_bounds__(kMaxBlock) void blob_chroma_meta_kernel(BlobArgs a,
     if (lane < take) {
       const u32x2 ent = ld64(qbase_s + 8u * (uint32_t)lane);
       const uint32_t w = ent.x;
-      const uint32_t d = ld16(kLdsRuns + 2u * chroma_of(w));
-      const uint32_t lo = d & 0xFFu, hi = d >> 8, Y0 = w & 0xFFu, Y1 = (w >> 16) & 0xFFu;
+      const uint32_t c = chroma_of(w);
+      const uint32_t d = ld16(kLdsRuns + 2u * c), A = ld8(kLdsBlocks + 2u * (c >> 4));
+      const uint32_t lo = d & 0xFFu, hi = d >> 8, Y0 = (w - A) & 0xFFu, Y1 = ((w >> 16) - A) & 0xFFu;
       const bool xw = d == kChromaExc;
       const bool f0 = xw | ((Y0 < lo) & (Y0 > hi)), f1 = xw | ((Y1 < lo) & (Y1 > hi));
       const uint32_t n = (f0 ? exact_mask<0>(w) & 1u : 0u) + (f1 ? exact_mask<1>(w) & 1u : 0u);
@@ -1296,7 +1330,7 @@ __global__ __launch_bounds__(kMaxBlock) void blob_chroma_meta_kernel(BlobArgs a,
           cut[i] = ld16(kLdsBlocks + ((c >> 11) & 0x1FFEu));
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) mm[i] = ld64(kLdsPairs + (cut[i] & 0xFFu));
+        for (int i = 0; i < 4; ++i) mm[i] = ld64(kLdsPairs + (cut[i] >> 8));
 #pragma unroll
         for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(d[i]), "+v"(cut[i]));
 #pragma unroll

@@ -62,17 +62,19 @@ static_assert(2 * sizeof(StripeTables) <= 160 * 1024, "two workgroups per CU");
 
 // Tables of the chroma-run kernel (trik_hsv_chroma.hip), one set per group of
 // <= 4 ranges, built on the device from RangeTables:
-//   runs[c]     : descriptor b1 | b2 << 8 of chroma c = U | V << 8: the
-//                 fast path's mask is Y >= A && Y <= b2 ? (Y < b1 ? M1 : M2) : 0
-//                 (A: the block's cut); with b1 > b2 + 1 the pixels
-//                 b2 < Y < b1 go to the exact path (a "window", always above
-//                 A), and kChromaExc sends both pixels there
+//   runs[c]     : descriptor b1 | b2 << 8 of chroma c = U | V << 8, both
+//                 stored relative to the block's cut A: with t = (Y - A) mod
+//                 256 the fast path's mask is t <= b2 ? (t < b1 ? M1 : M2) : 0
+//                 (Y < A wraps above every b1, b2 <= 255 - A: 0); with
+//                 b1 > b2 + 1 the pixels b2 < t < b1 go to the exact path (a
+//                 "window", always above A), and kChromaExc (not relative)
+//                 sends both pixels there
 //   summary[c]  : builder scratch (run summary of the chroma's profile)
 constexpr uint32_t kChromaExc = 0x00FFu;  // b1 = 255, b2 = 0: the builder never makes this window
-//   blocks[b]   : low byte: 8 x the palette slot of block b's mask pair (the
-//                 hot kernel's LDS offset of the pair); high byte: the block's
-//                 leading-zero cut A: pixels with Y < A are 0 (the
-//                 fast path masks them), so a chroma whose profile is zero
+//   blocks[b]   : high byte: 8 x the palette slot of block b's mask pair (the
+//                 hot kernel's LDS offset of the pair); low byte: the block's
+//                 leading-zero cut A: pixels with Y < A are 0 (one packed
+//                 subtract takes A from both Y), so a chroma whose profile is zero
 //                 below A describes only its profile from A on -- the
 //                 0 | M1 | M2 | 0 profiles of overlapping ranges become runs
 //   palette     : the byte-spread (M1, M2) of each palette slot; palette_of[k]

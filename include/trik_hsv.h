@@ -176,7 +176,7 @@ typedef struct TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg {
   uint8_t detectSatTol;
   uint8_t detectVal;     /* [0..100] */
   uint8_t detectValTol;
-  int32_t autoDetectHsv; /* not reproduced (srand(time) annealing); detect* untouched */
+  int32_t autoDetectHsv; /* ignored unless trik_hsv_set_auto_detect(handle, 1) */
 } TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg;
 
 typedef struct TRIK_VIDTRANSCODE_CV_OV7670_InArgs { /* OPUB:62-65 */
@@ -339,7 +339,8 @@ int32_t TRIK_VIDTRANSCODE_CV_create(const TRIK_VIDTRANSCODE_CV_Params* params,
  * LineDetector::run (LSEQ:376-476): V-range detection in columns 5..W-5,
  * cross points over rows H/2..H/2+80, its preview overlays; OutArgs.targetY
  * is the cross size.  autoDetectHsv is ignored (the line sensor's detector is
- * seeded by srand(time(NULL))). */
+ * seeded by srand(time(NULL))) unless trik_hsv_set_auto_detect asks for the
+ * exact search. */
 int32_t TRIK_VIDTRANSCODE_CV_create_line(const TRIK_VIDTRANSCODE_CV_Params* params,
                                          TRIK_VIDTRANSCODE_CV_Handle* out_handle);
 
@@ -353,7 +354,8 @@ int32_t TRIK_VIDTRANSCODE_CV_create_line(const TRIK_VIDTRANSCODE_CV_Params* para
  * 200) / W of the mean column, targetY = 0, targetSize = N * 100 / (W * H);
  * the preview is every pixel (matches white) with magenta lines at columns
  * W/2 +- 40 and +- 80 and a red 3-column line at the mean column.
- * autoDetectHsv is ignored (its detector is seeded by srand(time(NULL))). */
+ * autoDetectHsv is ignored (its detector is seeded by srand(time(NULL)))
+ * unless trik_hsv_set_auto_detect asks for the exact search. */
 int32_t TRIK_VIDTRANSCODE_CV_create_webcam_line(const TRIK_VIDTRANSCODE_CV_Params* params,
                                                 TRIK_VIDTRANSCODE_CV_Handle* out_handle);
 
@@ -722,6 +724,70 @@ int32_t trik_hsv_batch_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsv
  * detectHueTolerance, detectSat, detectSatTolerance, detectVal,
  * detectValTolerance (uint16), as OutArgsAlg receives them. */
 int32_t trik_hsv_batch_auto_range(const TrikHsvFrameBatch* batch, uint16_t* out_dev, void* hip_stream);
+
+/* Deterministic autoDetectHsv of the ov7670 object sensor and the two line
+ * sensors.  Their detectors (ODET = trik/ov7670/object_sensor/
+ * include/internal/cv_hsv_range_detector.hpp; LDET, LDETW = the copies under
+ * trik/ov7670/line_sensor and trik/webcam/line_sensor) build a signed score
+ * histogram of the whole frame (+1 per pixel of the positive zone, -2 per
+ * pixel of the negative zone), remember a start cell, and then anneal from a
+ * clock seed towards the box (interval) that maximises
+ * sum(score != 0 ? score : -K0).  The histogram and the start cell are
+ * reproduced bit for bit; the annealing is replaced by the exact maximum of
+ * the same objective under a fixed tie rule; the output scaling is the
+ * reference's.
+ *   kind                          layout  bins                 K0
+ *   TRIK_HSV_AUTO_OV7670_OBJECT   ov7670  32 x 32 [H>>3][S>>3]  2   (ODET:200-227)
+ *   TRIK_HSV_AUTO_OV7670_LINE     ov7670  256 [V]               1   (LDET:215-240)
+ *   TRIK_HSV_AUTO_WEBCAM_LINE     YUYV    256 [V]               1   (LDETW:215-240)
+ * Each call fails (trik_hsv_last_error()) and writes nothing for an unknown
+ * kind, a layout that is not the kind's, or a side above 2048. */
+#define TRIK_HSV_AUTO_OV7670_OBJECT 0
+#define TRIK_HSV_AUTO_OV7670_LINE 1
+#define TRIK_HSV_AUTO_WEBCAM_LINE 2
+#define TRIK_HSV_AUTO_MAX_SIDE 2048
+
+/* The deterministic half, for a caller with a search of their own:
+ *   scores_dev  [N][1024] int32 (object kind, bin h * 32 + s) or [N][256]: the
+ *               final histogram;
+ *   start_dev   [N][4] int32: the start cell's h (or v), its s (or 0), the
+ *               detector's max_value, 0.  The start cell is the cell whose
+ *               running value first reaches the largest value any cell holds
+ *               right after one of its positive pixels, in raster order;
+ *               (0, 0) with max_value 0 when no such value is positive (the
+ *               line detectors leave the cell uninitialised there). */
+int32_t trik_hsv_auto_scores(const TrikHsvFrameBatch* batch, int32_t kind, int32_t* scores_dev, int32_t* start_dev,
+                             void* hip_stream);
+
+/* The whole detector with the exact search:
+ *   out_dev   [N][6] uint16: detectHue, detectHueTolerance, detectSat,
+ *             detectSatTolerance, detectVal, detectValTolerance;
+ *   best_dev  optional [N][5] int32: the maximum L and its box h1, h2, s1, s2
+ *             (line kinds: v0, v1, 0, 0).
+ * Object kind: over h1, h2 in 0..31 (h1 > h2 wraps through 31 -> 0), s1 in
+ * 0..s_start, s2 in s_start..31 -- every state the annealing can visit --
+ * the largest m_foo (ODET:109-153); ties go to the fewest cells, then the
+ * smallest h1, then the smallest s1, then the smallest h2.  Line kinds: over
+ * 0 <= v0 <= v1 <= 255 the largest F (LDET:137-163); ties go to the shortest
+ * interval, then the smallest v0. */
+int32_t trik_hsv_batch_auto_range_exact(const TrikHsvFrameBatch* batch, int32_t kind, uint16_t* out_dev,
+                                        int32_t* best_dev, void* hip_stream);
+
+/* The detectors' output scaling of a box (ODET:271-293; LDET:280-303, LDETW
+ * the same with (v1 + 1) - 1 for v1 + 1): fp32 products truncated to int
+ * (uint8_t for the line kinds' bounds).  Line kinds take v0, v1 as h1, h2 and
+ * ignore s1, s2.  Needs 0 <= h1, h2 <= 31 and 0 <= s1 <= s2 <= 31, or 0 <= v0
+ * <= v1 <= 255.  Host code, no GPU call; the device path gives the same. */
+int32_t trik_hsv_auto_range_of(int32_t kind, int32_t h1, int32_t h2, int32_t s1, int32_t s2, uint16_t out[6]);
+
+/* autoDetectHsv of the ov7670 object sensor's, the ov7670 line sensor's and
+ * the webcam line sensor's process().  Mode 0 (the default): InArgs
+ * autoDetectHsv is ignored and OutArgs detect* are left untouched.  Mode 1:
+ * when InArgs autoDetectHsv is set, and only then, detect* receive
+ * trik_hsv_batch_auto_range_exact of the frame; targets and preview are the
+ * same.  Returns the previous mode, or -1 (trik_hsv_last_error()) for a NULL
+ * handle, another codec's handle or an unknown mode. */
+int32_t trik_hsv_set_auto_detect(TRIK_VIDTRANSCODE_CV_Handle handle, int32_t mode);
 
 /* The line sensor for N ov7670 frames: sums_dev[i] =
  * {points, sum_x, cross points} -- cross points in the sum_y slot -- for V in

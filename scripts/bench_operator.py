@@ -9,6 +9,11 @@
   line        trik_hsv_line_batch: 4096 x 640x480 ov7670 (YUV422P) frames, the
               line sensor's sums + OutArgs; algorithmic bytes = both planes
               (2 B/px) once.  line_preview: its 320x240 previews.
+  autorange_exact  trik_hsv_batch_auto_range_exact (and trik_hsv_auto_scores):
+              the exact autoDetectHsv of the ov7670 object sensor, the ov7670
+              line sensor and the webcam line sensor over 4096 frames of 320x240
+              and of 640x480, scene and uniform random bytes, the line sensor on
+              the same geometry beside them; algorithmic bytes = 2 B/px once.
   blob        trik_hsv_blob_batch: 4096 x 640x480 ov7670 frames through the
               multi-blob sensor (metapixel bitmap + clusterer + 8 targets).
   edge        trik_hsv_edge_batch: the edge-line sensor's sums + OutArgs over
@@ -65,6 +70,8 @@ def main():
     ap.add_argument("--frames", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--no-cpu", action="store_true", help="skip the oracle CPU baselines")
+    ap.add_argument("--only-autorange", action="store_true",
+                    help="stop after the preview, auto_range, line and autorange_exact rows")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -108,6 +115,40 @@ def main():
                    "achieved_GBs": round(lf * lfb / (ln_ms / 1e3) / 1e9, 1),
                    "hbm_frac": round(lf * lfb / (ln_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                    "note": "line_vec_kernel + line_targets_kernel"}
+    # the exact autoDetectHsv of the ov7670 object sensor and the two line
+    # sensors, beside the webcam object sensor's auto_range row and the line
+    # row above: one workgroup per frame, a barrier pair per row of the
+    # positive band (every row for the line kinds)
+    out["autorange_exact"] = {"frames": lf,
+                              "note": "auto_exact_kernel (histogram + start cell + exact search + scaling, one launch); "
+                                      "bytes_algorithmic = 2 B/px once: both planes (ov7670 kinds) or the YUYV frame "
+                                      "(webcam line); over_line: against trik_hsv_line_batch on the same geometry"}
+    kinds = (("ov7670_object", trik_hsv.AUTO_OV7670_OBJECT), ("ov7670_line", trik_hsv.AUTO_OV7670_LINE),
+             ("webcam_line", trik_hsv.AUTO_WEBCAM_LINE))
+    for aw, ah in ((320, 240), (W, H)):
+        adev = torch.empty(lf * 2 * ah * aw, dtype=torch.uint8, device="cuda")
+        aln_ms = None
+        for fill, name in ((1, "scene"), (0, "uniform")):
+            for kname, kind in kinds:
+                lay = trik_hsv.LAYOUT_YUYV if kind == trik_hsv.AUTO_WEBCAM_LINE else trik_hsv.LAYOUT_OV7670
+                all_ = 2 * aw if lay == trik_hsv.LAYOUT_YUYV else aw
+                trik_hsv.synth(adev, aw, ah, all_, lay, fill, 0x7A1C)
+                if aln_ms is None:  # (the first pass: ov7670 scene frames)
+                    aln_ms = timed(lambda: trik_hsv.line_batch(adev, aw, ah, aw, 0, 30), stream, args.iters)
+                ms = timed(lambda: trik_hsv.batch_auto_range_exact(adev, aw, ah, all_, kind), stream, args.iters)
+                sc_ms = timed(lambda: trik_hsv.auto_scores(adev, aw, ah, all_, kind), stream, args.iters)
+                nb = lf * 2 * aw * ah
+                out["autorange_exact"][f"{aw}x{ah}_{name}_{kname}"] = {
+                    "ms": round(ms, 4), "scores_only_ms": round(sc_ms, 4), "Mframes_per_s": round(lf / ms / 1e3, 3),
+                    "bytes_algorithmic": nb, "achieved_GBs": round(nb / (ms / 1e3) / 1e9, 1),
+                    "hbm_frac": round(nb / (ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4), "line_ms": round(aln_ms, 4),
+                    "over_line": round(ms / aln_ms, 2)}
+        del adev
+    if args.only_autorange:
+        det.close()
+        print(json.dumps(out))
+        return
+
     lsums, _ = trik_hsv.line_batch(ldev, W, H, W, 0, 30)
     lp_ms = timed(lambda: det.line_preview(ldev, W, H, W, 0, 30, lsums, out_width=OW, out_height=OH,
                                            out_line_length=OLL), stream, args.iters)

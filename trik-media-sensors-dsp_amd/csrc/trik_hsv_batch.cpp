@@ -186,6 +186,69 @@ extern "C" int32_t trik_hsv_batch_auto_range(const TrikHsvFrameBatch* b, uint16_
   return 0;
 }
 
+namespace {
+
+// The batch, then the kind against its layout and the side cap.
+int32_t check_auto_exact(const TrikHsvFrameBatch* b, int32_t kind) {
+  const int32_t rc = check_batch(b);
+  if (rc) return rc;
+  const std::string e = auto_exact_error(kind, b->layout, b->width, b->height);
+  return e.empty() ? 0 : fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+}
+
+}  // namespace
+
+extern "C" int32_t trik_hsv_auto_scores(const TrikHsvFrameBatch* b, int32_t kind, int32_t* scores, int32_t* start,
+                                        void* stream) {
+  const int32_t rc = check_auto_exact(b, kind);
+  if (rc) return rc;
+  if (b->n_frames > 0 && (!scores || !start)) return fail(TRIK_IVIDTRANSCODE_EFAIL, "auto_scores: NULL buffer");
+  HIP_TRY(launch_auto_exact(auto_exact_args(*b, kind, scores, start, nullptr, nullptr),
+                            static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_batch_auto_range_exact(const TrikHsvFrameBatch* b, int32_t kind, uint16_t* out,
+                                                   int32_t* best, void* stream) {
+  const int32_t rc = check_auto_exact(b, kind);
+  if (rc) return rc;
+  if (b->n_frames > 0 && !out) return fail(TRIK_IVIDTRANSCODE_EFAIL, "out is NULL");
+  HIP_TRY(launch_auto_exact(auto_exact_args(*b, kind, nullptr, nullptr, out, best),
+                            static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_auto_range_of(int32_t kind, int32_t h1, int32_t h2, int32_t s1, int32_t s2,
+                                          uint16_t out[6]) {
+  if (!out) return fail(TRIK_IVIDTRANSCODE_EFAIL, "auto_range_of: out is NULL");
+  if (kind == TRIK_HSV_AUTO_OV7670_OBJECT) {
+    if (h1 < 0 || h1 > 31 || h2 < 0 || h2 > 31 || s1 < 0 || s2 > 31 || s1 > s2)
+      return fail(TRIK_IVIDTRANSCODE_EFAIL, "auto_range_of: need 0 <= h1, h2 <= 31 and 0 <= s1 <= s2 <= 31");
+  } else if (kind == TRIK_HSV_AUTO_OV7670_LINE || kind == TRIK_HSV_AUTO_WEBCAM_LINE) {
+    if (h1 < 0 || h2 > 255 || h1 > h2) return fail(TRIK_IVIDTRANSCODE_EFAIL, "auto_range_of: need 0 <= v0 <= v1 <= 255");
+  } else {
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "auto range: unknown kind " + std::to_string(kind));
+  }
+  auto_range_scale(kind, h1, h2, s1, s2, out);
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_set_auto_detect(TRIK_VIDTRANSCODE_CV_Handle h, int32_t mode) {
+  if (!h) {
+    fail(TRIK_IVIDTRANSCODE_EFAIL, "handle is NULL");
+    return -1;
+  }
+  if (h->algo != kAlgoBlob && h->algo != kAlgoLine && h->algo != kAlgoWLine) {
+    fail(TRIK_IVIDTRANSCODE_EFAIL, "set_auto_detect: only the ov7670 object sensor and the line sensors take it");
+    return -1;
+  }
+  if (mode != 0 && mode != 1) {
+    fail(TRIK_IVIDTRANSCODE_EFAIL, "set_auto_detect: mode must be 0 or 1");
+    return -1;
+  }
+  return h->auto_detect.exchange(mode);
+}
+
 extern "C" int32_t trik_hsv_line_batch(const TrikHsvFrameBatch* b, int32_t val_from, int32_t val_to,
                                        int32_t band_start, int32_t band_stop, TrikHsvTargetSums* sums,
                                        TrikHsvTarget* targets, void* stream) {

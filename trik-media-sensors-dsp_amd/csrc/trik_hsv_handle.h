@@ -245,6 +245,9 @@ struct TrikCvHandle {
   // trik_hsv_last_hot_kernel
   std::atomic<int> hot{TRIK_HSV_HOT_AUTO};
   std::atomic<int> reserved_cus{0};  // trik_hsv_set_reserved_cus
+  // trik_hsv_set_auto_detect: 1 = process() of the ov7670 object sensor and
+  // the line sensors answers InArgs autoDetectHsv with the exact search
+  std::atomic<int> auto_detect{0};
   std::vector<int8_t> hot_groups;
   TableSet* pending_set = nullptr;
 
@@ -390,6 +393,9 @@ LineArgs line_args(const TrikHsvFrameBatch& b, int val_from, int val_to, int ban
                    TrikHsvTargetSums* sums, TrikHsvTarget* targets);
 TRIK_VIDTRANSCODE_CV_InArgsAlg blob_range_args(const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg& a);
 AutoRangeArgs auto_range_args(const TrikHsvFrameBatch& b, uint16_t* out);
+// the exact-search detectors (kind and geometry validated: auto_exact_error)
+AutoExactArgs auto_exact_args(const TrikHsvFrameBatch& b, int kind, int32_t* scores, int32_t* start, uint16_t* out,
+                              int32_t* best);
 // the object sensor's preview: body, guide lines and the circle from sums
 int32_t preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
                      const TrikHsvTargetSums* sums, int sums_pitch, int ow, int oh, int oll, uint8_t* previews,

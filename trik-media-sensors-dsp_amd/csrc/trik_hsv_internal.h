@@ -251,6 +251,66 @@ struct AutoRangeArgs {
   uint16_t* out;
 };
 
+// Deterministic autoDetectHsv of the ov7670 object sensor and the two line
+// sensors (trik_hsv_autorange.hip; include/trik_hsv.h for ODET, LDET, LDETW;
+// DESIGN.md 4.9).  The zones are the detectors' own comparisons on plain ints
+// (auto_exact_zone): a pixel is positive when pc_lo < col < pc_hi and pr_lo <
+// row < pr_hi; otherwise negative when col < nc_lo, col > nc_hi, row < nr_lo
+// or row > nr_hi.
+constexpr int kAutoObjectBins = 32 * 32;
+constexpr int kAutoLineBins = 256;
+struct AutoExactArgs {
+  const uint8_t* frames;
+  int64_t frame_stride;
+  int32_t n_frames, width, height, line_length, layout;
+  int32_t kind;  // TRIK_HSV_AUTO_*
+  int32_t pc_lo, pc_hi, pr_lo, pr_hi;
+  int32_t nc_lo, nc_hi, nr_lo, nr_hi;
+  int32_t* scores;  // optional [n][bins]: the final histogram
+  int32_t* start;   // optional [n][4]: start h (v), s (0), max_value, 0
+  uint16_t* out;    // optional [n][6]: the exact search's box, scaled; with best
+  int32_t* best;    // optional [n][5]: L, h1, h2, s1, s2 (v0, v1, 0, 0)
+};
+inline int auto_bins(int kind) { return kind == TRIK_HSV_AUTO_OV7670_OBJECT ? kAutoObjectBins : kAutoLineBins; }
+// "" when the kind exists, the layout is the kind's and both sides are at
+// most TRIK_HSV_AUTO_MAX_SIDE (the scores stay within int32 there)
+std::string auto_exact_error(int kind, int layout, int64_t width, int64_t height);
+// ODET:156-175 (zone scale 6, OSEQ) and LDET:165-187 (step 40, uint16 ROI)
+void auto_exact_zone(AutoExactArgs& a);
+int launch_auto_exact(const AutoExactArgs& a, hipStream_t s);
+
+// The detectors' output scaling of a box (ODET:271-293; LDET:280-303; LDETW
+// the same with v1 for v1 + 1), for the host call and the search kernel
+// alike: one fp32 product per bound, truncated.
+__host__ __device__ inline void auto_range_scale(int kind, int h1, int h2, int s1, int s2, uint16_t* out) {
+  if (kind == TRIK_HSV_AUTO_OV7670_OBJECT) {
+    h1 = (int)((float)(h1 << 3) * 1.4f);
+    h2 = (int)((float)(((h2 + 1) << 3) - 1) * 1.4f);
+    s1 = (int)((float)(s1 << 3) * 0.39f);
+    s2 = (int)((float)((s2 + 1) << 3) * 0.39f);
+    if (h1 <= h2) {
+      out[0] = (uint16_t)((h2 + h1) / 2);
+      out[1] = (uint16_t)((h2 - h1) / 2);
+    } else {
+      const float hue = ((float)h2 - (360.0f - (float)h1)) / 2;
+      const float tol = ((float)h2 + (360.0f - (float)h1)) / 2;
+      out[0] = (uint16_t)(int)(hue >= 0 ? hue : hue + 360);
+      out[1] = (uint16_t)(int)tol;
+    }
+    out[2] = (uint16_t)((s2 + s1) / 2);
+    out[3] = (uint16_t)((s2 - s1) / 2 + 2);
+    out[4] = 50;
+    out[5] = 50;
+  } else {
+    const int top = kind == TRIK_HSV_AUTO_OV7670_LINE ? h2 + 1 : (h2 + 1) - 1;
+    const int v0 = (uint8_t)(int)((float)h1 * 0.39f);
+    const int v1 = (uint8_t)(int)((float)top * 0.39f);
+    out[0] = out[1] = out[2] = out[3] = 0;
+    out[4] = (uint16_t)((v1 + v0) / 2);
+    out[5] = (uint16_t)((v1 - v0) / 2);
+  }
+}
+
 // ov7670 line sensor of N frames (trik_hsv_line.hip).  sums[f] = {N, sumX,
 // crossPoints} (crossPoints in the sum_y slot), zeroed by the caller.
 struct LineArgs {

@@ -31,18 +31,7 @@ namespace trik_hsv {
 
 namespace {
 
-struct Luts {
-  uint16_t l43[256], l255[256];
-};
-constexpr Luts make_luts() {  // WSEQ:400-406
-  Luts l{};
-  for (uint32_t i = 1; i < 256; ++i) {
-    l.l43[i] = (uint16_t)((43u * 256u) / i);
-    l.l255[i] = (uint16_t)((255u * 256u) / i);
-  }
-  return l;
-}
-__constant__ Luts c_luts = make_luts();
+__constant__ Luts c_luts = make_luts();  // trik_hsv_pixel.h
 
 
 // The preview as a grid-stride gather over 4-byte output groups (two output

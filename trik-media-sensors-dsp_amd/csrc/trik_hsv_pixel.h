@@ -69,6 +69,20 @@ __device__ __forceinline__ bool detect_packed(uint32_t H, uint32_t S, uint32_t V
   return out == r.expect;
 }
 
+// s_mult43_div and s_mult255_div (WSEQ:400-406) as a compile-time image: a
+// kernel file that needs them outside RangeTables keeps one __constant__ copy.
+struct Luts {
+  uint16_t l43[256], l255[256];
+};
+constexpr Luts make_luts() {
+  Luts l{};
+  for (uint32_t i = 1; i < 256; ++i) {
+    l.l43[i] = (uint16_t)((43u * 256u) / i);
+    l.l255[i] = (uint16_t)((255u * 256u) / i);
+  }
+  return l;
+}
+
 // H, S, V bytes (WSEQ:207-249) with LUT43 / LUT255 from any address space.
 template <typename L>
 __device__ __forceinline__ void pixel_hsv_bytes(const PixelRgb& p, const L* l43, const L* l255, uint32_t& H,

@@ -77,16 +77,47 @@ int32_t process_ball(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
 }
 
 // The three sensors below ignore autoDetectHsv and leave OutArgs.detect*
-// untouched: their range detectors are simulated annealings seeded by
-// srand(time(NULL)) (the webcam line sensor's cv_hsv_range_detector.hpp:200)
-// -- not reproducible.
+// untouched by default: their range detectors are simulated annealings seeded
+// by srand(time(NULL)) (the webcam line sensor's cv_hsv_range_detector.hpp:200)
+// -- not reproducible.  With trik_hsv_set_auto_detect(handle, 1) a set
+// autoDetectHsv is answered by the exact maximum of the detector's own
+// objective over its bit-exact score histogram (trik_hsv_autorange.hip,
+// DESIGN.md 4.9): deterministic, never worse by the reference's measure.
+struct AutoDetect {
+  bool on = false;
+  uint16_t detect[6] = {0, 0, 0, 0, 0, 0};
+};
+
+// Enqueues the exact search of the staged frame and its readback when the
+// handle's mode and InArgs ask for it; the caller's read_back synchronises.
+int32_t enqueue_auto_detect(TrikCvHandle* h, const TrikHsvFrameBatch& b, int kind, int32_t auto_detect_hsv,
+                            AutoDetect& ad) {
+  ad.on = auto_detect_hsv != 0 && h->auto_detect.load() == 1;
+  if (!ad.on) return 0;
+  const std::string e = auto_exact_error(kind, b.layout, b.width, b.height);
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  if (!h->d_auto) HIP_TRY(hipMalloc(&h->d_auto, 6 * sizeof(uint16_t)));
+  HIP_TRY(launch_auto_exact(auto_exact_args(b, kind, nullptr, nullptr, h->d_auto, nullptr), h->stream));
+  HIP_TRY(hipMemcpyAsync(ad.detect, h->d_auto, sizeof ad.detect, hipMemcpyDeviceToHost, h->stream));
+  return 0;
+}
+
+template <typename OutArgsAlg>
+void set_detect(OutArgsAlg& oa, const AutoDetect& ad) {
+  if (!ad.on) return;
+  oa.detectHue = ad.detect[0]; oa.detectHueTolerance = ad.detect[1];
+  oa.detectSat = ad.detect[2]; oa.detectSatTolerance = ad.detect[3];
+  oa.detectVal = ad.detect[4]; oa.detectValTolerance = ad.detect[5];
+}
 
 // LineDetector::run, LSEQ:376-476
 int32_t process_line(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewOut& pv,
                      const TRIK_VIDTRANSCODE_CV_InArgsAlg& ia, TRIK_VIDTRANSCODE_CV_OutArgsAlg& oa) {
   HIP_TRY(launch_line(line_args(b, ia.detectValFrom, ia.detectValTo, h->line_band[0], h->line_band[1], h->d_sums,
                                 h->d_targets), h->stream));
-  int32_t r = 0;
+  AutoDetect ad;
+  int32_t r = enqueue_auto_detect(h, b, TRIK_HSV_AUTO_OV7670_LINE, ia.autoDetectHsv, ad);
+  if (r) return r;
   if (pv.bytes) {  // preview: window columns only, then the overlays
     r = line_preview_core(h, b, line_alg(ia.detectValFrom, ia.detectValTo), 5, h->in_w - 5, 1, h->d_sums,
                           h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes, h->stream);
@@ -96,6 +127,7 @@ int32_t process_line(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
   r = read_back(h, pv, h->d_targets, &t, 1);
   if (r) return r;
   set_target(oa, t);
+  set_detect(oa, ad);
   h->line_band[0] = h->in_h / 2;  // LSEQ:449-450, read by the next run
   h->line_band[1] = h->in_h / 2 + 80;
   return 0;
@@ -109,6 +141,9 @@ int32_t process_wline(TrikCvHandle* h, const TrikHsvFrameBatch& b, const Preview
   int32_t r = run_sums(h, &b, &wr, 1, h->d_sums, nullptr, h->stream);
   if (r) return r;
   HIP_TRY(launch_wline_targets(1, h->in_w, h->in_h, h->d_sums, h->d_targets, h->stream));
+  AutoDetect ad;
+  r = enqueue_auto_detect(h, b, TRIK_HSV_AUTO_WEBCAM_LINE, ia.autoDetectHsv, ad);
+  if (r) return r;
   if (pv.bytes) {  // every pixel (LSEQW:232-269), then the thin and target lines
     r = line_preview_core(h, b, wr, 0, 0x7FFFFFFF, 0, h->d_sums, h->out_w, h->out_h, h->out_ll, h->d_preview,
                           (int64_t)pv.bytes, h->stream);
@@ -118,6 +153,7 @@ int32_t process_wline(TrikCvHandle* h, const TrikHsvFrameBatch& b, const Preview
   r = read_back(h, pv, h->d_targets, &t, 1);
   if (r) return r;
   set_target(oa, t);
+  set_detect(oa, ad);
   return 0;
 }
 
@@ -127,6 +163,9 @@ int32_t process_blob(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
   if (ia.setHsvRange) h->blob_range = blob_range_args(ia);  // BMB:110-130
   BlobArgs ba;
   int32_t r = blob_core(h, b, h->blob_range, nullptr, nullptr, nullptr, nullptr, nullptr, h->stream, ba);
+  if (r) return r;
+  AutoDetect ad;  // OSEQ:537-544
+  r = enqueue_auto_detect(h, b, TRIK_HSV_AUTO_OV7670_OBJECT, ia.autoDetectHsv, ad);
   if (r) return r;
   if (pv.bytes) {  // preview: set metapixels, guide lines, target marks
     r = blob_preview_core(h, b, ba.meta, ba.top, h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes,
@@ -141,6 +180,7 @@ int32_t process_blob(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
     oa.target[i].y = t[i].y;
     oa.target[i].size = t[i].size;
   }
+  set_detect(oa, ad);
   return 0;
 }
 

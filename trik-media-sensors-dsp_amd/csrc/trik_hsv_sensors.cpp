@@ -222,6 +222,19 @@ AutoRangeArgs trik_hsv::auto_range_args(const TrikHsvFrameBatch& b, uint16_t* ou
   return a;
 }
 
+AutoExactArgs trik_hsv::auto_exact_args(const TrikHsvFrameBatch& b, int kind, int32_t* scores, int32_t* start,
+                                        uint16_t* out, int32_t* best) {
+  AutoExactArgs a;
+  a.frames = static_cast<const uint8_t*>(b.frames);
+  a.frame_stride = b.frame_stride;
+  a.n_frames = b.n_frames;
+  a.width = b.width; a.height = b.height; a.line_length = b.line_length; a.layout = b.layout;
+  a.kind = kind;
+  auto_exact_zone(a);
+  a.scores = scores; a.start = start; a.out = out; a.best = best;
+  return a;
+}
+
 namespace {
 
 // Scratch for n frames of W x H.  Stream s waits (device side) for the

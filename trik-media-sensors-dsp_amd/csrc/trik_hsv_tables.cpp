@@ -349,4 +349,38 @@ void auto_range_zone(int width, int height, int32_t& c_lo, int32_t& c_hi, int32_
   r_hi = (uint16_t)(h_height + step);
 }
 
+std::string auto_exact_error(int kind, int layout, int64_t width, int64_t height) {
+  if (kind != TRIK_HSV_AUTO_OV7670_OBJECT && kind != TRIK_HSV_AUTO_OV7670_LINE && kind != TRIK_HSV_AUTO_WEBCAM_LINE)
+    return "auto range: unknown kind " + std::to_string(kind);
+  if (layout != (kind == TRIK_HSV_AUTO_WEBCAM_LINE ? TRIK_HSV_LAYOUT_YUYV : TRIK_HSV_LAYOUT_OV7670))
+    return kind == TRIK_HSV_AUTO_WEBCAM_LINE ? "auto range: the webcam line kind takes the YUYV layout (YUV422)"
+                                             : "auto range: the ov7670 kinds take the ov7670 layout (YUV422P)";
+  if (width > TRIK_HSV_AUTO_MAX_SIDE || height > TRIK_HSV_AUTO_MAX_SIDE)
+    return "auto range: need width, height <= 2048";
+  return "";
+}
+
+void auto_exact_zone(AutoExactArgs& a) {
+  if (a.kind == TRIK_HSV_AUTO_OV7670_OBJECT) {  // ODET:156-175, plain int bounds, zone scale 6 (OSEQ)
+    const int hh = a.height / 2, hw = a.width / 2, step = a.height / 6;
+    a.pc_lo = hw - step; a.pc_hi = hw + step;
+    a.pr_lo = hh - step; a.pr_hi = hh + step;
+    a.nc_lo = hw - 2 * step; a.nc_hi = hw + 2 * step;
+    a.nr_lo = hh - 2 * step; a.nr_hi = hh + 2 * step;
+    return;
+  }
+  // LDET:165-187 with step 40 (LSEQ:430): uint16_t fields, so the bounds of a
+  // narrow frame wrap modulo 2^16; the comparisons then promote them to int
+  const uint16_t h_width = (uint16_t)(a.width / 2), step = 40;
+  const uint16_t left_p = (uint16_t)(h_width - step), right_p = (uint16_t)(h_width + step);
+  a.pc_lo = left_p;
+  a.pc_hi = right_p;
+  a.nc_lo = (uint16_t)(left_p - step);
+  a.nc_hi = (uint16_t)(right_p + step);
+  a.pr_lo = -1;  // every row
+  a.pr_hi = a.height;
+  a.nr_lo = INT32_MIN;  // no row test
+  a.nr_hi = INT32_MAX;
+}
+
 }  // namespace trik_hsv

@@ -470,6 +470,65 @@ def batch_auto_range(frames, width, height, line_length, layout, *, n_frames=Non
     return out
 
 
+# the detectors behind trik_hsv_auto_scores / trik_hsv_batch_auto_range_exact
+AUTO_OV7670_OBJECT, AUTO_OV7670_LINE, AUTO_WEBCAM_LINE = 0, 1, 2
+AUTO_MAX_SIDE = 2048
+
+
+def _auto_layout(kind: int) -> int:
+    return LAYOUT_YUYV if kind == AUTO_WEBCAM_LINE else LAYOUT_OV7670
+
+
+def auto_bins(kind: int) -> int:
+    """Bins of a kind's score histogram: 32 x 32 (H >> 3, S >> 3) or 256 (V)."""
+    return 1024 if kind == AUTO_OV7670_OBJECT else 256
+
+
+def auto_scores(frames, width, height, line_length, kind, *, n_frames=None, frame_stride=None, stream=None):
+    """The deterministic half of the ov7670 object sensor's and the line
+    sensors' autoDetectHsv (trik_hsv_auto_scores): the detector's final score
+    histogram int32 [N, bins] and start int32 [N, 4] = the start cell's h (or
+    v), s (or 0), max_value, 0."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, _auto_layout(kind), n_frames, frame_stride)
+    scores = torch.empty((b.n_frames, auto_bins(kind)), dtype=torch.int32, device=frames.device)
+    start = torch.empty((b.n_frames, 4), dtype=torch.int32, device=frames.device)
+    rc = _lib.trik_hsv_auto_scores(C.byref(b), int(kind), C.c_void_p(scores.data_ptr()),
+                                   C.c_void_p(start.data_ptr()), _stream_ptr(stream, frames))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_auto_scores")
+    return scores, start
+
+
+def batch_auto_range_exact(frames, width, height, line_length, kind, *, n_frames=None, frame_stride=None,
+                           stream=None):
+    """autoDetectHsv per frame by the exact search (trik_hsv_batch_auto_range_exact):
+    out int16 [N, 6] = hue, hueTol, sat, satTol, val, valTol (uint16 bits) and
+    best int32 [N, 5] = the maximum L and its box h1, h2, s1, s2 (v0, v1, 0, 0
+    for the line kinds)."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, _auto_layout(kind), n_frames, frame_stride)
+    out = torch.empty((b.n_frames, 6), dtype=torch.int16, device=frames.device)
+    best = torch.empty((b.n_frames, 5), dtype=torch.int32, device=frames.device)
+    rc = _lib.trik_hsv_batch_auto_range_exact(C.byref(b), int(kind), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(best.data_ptr()), _stream_ptr(stream, frames))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_batch_auto_range_exact")
+    return out, best
+
+
+def auto_range_of(kind: int, h1: int, h2: int, s1: int = 0, s2: int = 0) -> Tuple[int, ...]:
+    """The detectors' output scaling of a box (line kinds: v0, v1 as h1, h2):
+    (hue, hueTol, sat, satTol, val, valTol).  trik_hsv_auto_range_of, host code."""
+    out = (C.c_uint16 * 6)()
+    rc = _lib.trik_hsv_auto_range_of(int(kind), int(h1), int(h2), int(s1), int(s2), out)
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_auto_range_of")
+    return tuple(int(v) for v in out)
+
+
 def batch_targets(sums, width, height, *, stream=None):
     """Epilogue only: sums int64 [N,T,3] -> targets int8 [N,T,4]."""
     import torch
@@ -734,11 +793,26 @@ class ObjectSensor(_HotKernel):
         return fr, ib, ob, keep
 
 
-class LineSensor(ObjectSensor):
+class _AutoDetect:
+    """autoDetectHsv of the three codecs whose detectors are annealings
+    (trik_hsv_set_auto_detect)."""
+
+    def set_auto_detect(self, mode: int) -> int:
+        """0 (the default): process() ignores autoDetectHsv and leaves
+        detect* untouched.  1: a set autoDetectHsv fills detect* from the
+        exact search (batch_auto_range_exact of the frame).  Returns the
+        previous mode."""
+        prev = _lib.trik_hsv_set_auto_detect(self._h, int(mode))
+        if prev < 0:
+            raise ValueError(f"set_auto_detect({mode}): {_abi.last_error()}")
+        return prev
+
+
+class LineSensor(_AutoDetect, ObjectSensor):
     """The ov7670 line sensor's codec instance (trik/ov7670/line_sensor glue,
     LineDetector<YUV422P, RGB565X>): same quartet, YUV422P input; process()
-    uses only detectValFrom/To of the range and ignores autoDetectHsv; OutArgs
-    targetY carries the cross size."""
+    uses only detectValFrom/To of the range and ignores autoDetectHsv unless
+    set_auto_detect(1); OutArgs targetY carries the cross size."""
 
     _create = "TRIK_VIDTRANSCODE_CV_create_line"
 
@@ -748,16 +822,16 @@ class LineSensor(ObjectSensor):
             self.params = _default_params(1, fmt_in=FORMAT_YUV422P)
 
 
-class WebcamLineSensor(ObjectSensor):
+class WebcamLineSensor(_AutoDetect, ObjectSensor):
     """The webcam line sensor's codec instance (trik/webcam/line_sensor glue,
     LineDetector<YUV422, RGB565X>): same quartet and InArgs/OutArgs as the
     object sensor, packed YUYV input; process() uses only detectValFrom/To,
-    targetY is always 0, autoDetectHsv is ignored."""
+    targetY is always 0, autoDetectHsv is ignored unless set_auto_detect(1)."""
 
     _create = "TRIK_VIDTRANSCODE_CV_create_webcam_line"
 
 
-class BlobSensor(ObjectSensor):
+class BlobSensor(_AutoDetect, ObjectSensor):
     """The ov7670 object sensor's codec instance (trik/ov7670/object_sensor:
     BallDetector<YUV422P, RGB565X> with BitmapBuilder + Clusterizer): its own
     InArgs (centre/tolerance, sticky via setHsvRange) and OutArgs (target[8])."""

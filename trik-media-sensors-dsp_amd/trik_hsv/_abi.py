@@ -233,6 +233,10 @@ PROTOTYPES = {
     "trik_hsv_batch_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(InArgsAlg), C.c_void_p,
                                 i32, i32, i32, i32, C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_batch_auto_range": ([C.POINTER(FrameBatch), C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_auto_scores": ([C.POINTER(FrameBatch), i32, C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_batch_auto_range_exact": ([C.POINTER(FrameBatch), i32, C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_auto_range_of": ([i32, i32, i32, i32, i32, C.POINTER(C.c_uint16)], i32),
+    "trik_hsv_set_auto_detect": ([C.c_void_p, i32], i32),
     "trik_hsv_line_batch": ([C.POINTER(FrameBatch), i32, i32, i32, i32, C.c_void_p, C.c_void_p,
                              C.c_void_p], i32),
     "trik_hsv_line_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,

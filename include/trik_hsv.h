@@ -822,8 +822,52 @@ int32_t trik_hsv_blob_batch(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFra
                             int32_t* top_dev, uint8_t* meta_dev, uint16_t* labels_dev,
                             int32_t* n_labels_dev, void* hip_stream);
 
-/* Its previews for N frames from meta_dev and top_dev of trik_hsv_blob_batch
- * (OSEQ:387-420, 548-580). */
+/* The multi-blob sensor for N frames and n_ranges HSV ranges per frame, from
+ * one read of the frames per group of 4 ranges.  The ranges come in the
+ * from/to form of trik_hsv_process_batch (autoDetectHsv is ignored; see
+ * trik_hsv_blob_range_of for the centre/tolerance form); the batch may be
+ * TRIK_HSV_LAYOUT_OV7670 or TRIK_HSV_LAYOUT_YUYV.  A slot is one (frame f,
+ * range t) pair, s = f * n_ranges + t, and every output is laid out by slot:
+ *   targets_dev  [N][T][8] TrikHsvTarget;
+ *   top_dev      optional [N][T][8][3] int32;
+ *   meta_dev     optional [N][T][H/4][W/4] uint8;
+ *   labels_dev   optional [N][T][H/4][W/4] uint16;
+ *   n_labels_dev optional [N][T] int32.
+ * On ov7670 frames slot (f, t) holds exactly what trik_hsv_blob_batch writes
+ * for frame f alone with range t; on YUYV frames (Y0 U Y1 V) what that call
+ * writes for the ov7670 frame with the same (Y, U, V) at every pixel (there U
+ * is the odd chroma byte and V the even one, OSEQ:369-373).  The reference
+ * carries the bitmap builder and the clusterer under trik/webcam/object_sensor
+ * as well, byte-identical to the ov7670 copies, but its webcam detector does
+ * not include them: the YUYV form is the reference's algorithm on its other
+ * input layout, not one of its builds.
+ * The batch is walked in chunks of whole frames of at most
+ * TRIK_HSV_BLOB_CHUNK_SLOTS slots (at least one frame), stream-ordered without
+ * host synchronisation, so the handle's scratch is that of a single-range
+ * call of TRIK_HSV_BLOB_CHUNK_SLOTS frames however large N * n_ranges is.
+ * The bitmaps always come from the stripe arithmetic:
+ * trik_hsv_set_hot_kernel does not affect this call, and
+ * trik_hsv_last_hot_kernel reports TRIK_HSV_HOT_STRIPE after it.
+ * Fails (trik_hsv_last_error()) and writes nothing for a NULL handle, batch,
+ * ranges or (N > 0) targets, an unknown layout, n_ranges outside
+ * 1..TRIK_HSV_MAX_RANGES, width % 32 or height % 4 not zero, width > 8192 or
+ * more than 30,000 labels.  n_frames == 0 returns 0 and touches nothing;
+ * width or height 0 zeroes targets, top and n_labels. */
+#define TRIK_HSV_BLOB_CHUNK_SLOTS 4096
+int32_t trik_hsv_blob_batch_ranges(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch,
+                                   const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n_ranges,
+                                   TrikHsvTarget* targets_dev, int32_t* top_dev, uint8_t* meta_dev,
+                                   uint16_t* labels_dev, int32_t* n_labels_dev, void* hip_stream);
+
+/* The from/to range trik_hsv_blob_batch uses for a centre/tolerance range
+ * (cv_bitmap_builder_reference.hpp:110-130: hue wraps in 0..359, saturation
+ * and value clip to 0..100; setHsvRange is not read, autoDetectHsv of *out is
+ * 0).  Host code, no GPU call.  Fails for a NULL argument. */
+int32_t trik_hsv_blob_range_of(const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg* hsv,
+                               TRIK_VIDTRANSCODE_CV_InArgsAlg* out);
+
+/* The multi-blob previews for N ov7670 frames from meta_dev and top_dev of
+ * trik_hsv_blob_batch (OSEQ:387-420, 548-580). */
 int32_t trik_hsv_blob_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch,
                               const uint8_t* meta_dev, const int32_t* top_dev, int32_t out_width,
                               int32_t out_height, int32_t out_line_length, uint8_t* previews_dev,

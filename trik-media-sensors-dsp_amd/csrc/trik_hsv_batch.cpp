@@ -314,6 +314,40 @@ extern "C" int32_t trik_hsv_blob_batch(TRIK_VIDTRANSCODE_CV_Handle h, const Trik
   return blob_core(h, *b, blob_range_args(*hsv), targets, top, meta, labels, n_labels, s, ba);
 }
 
+extern "C" int32_t trik_hsv_blob_batch_ranges(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                              const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int32_t n,
+                                              TrikHsvTarget* targets, int32_t* top, uint8_t* meta,
+                                              uint16_t* labels, int32_t* n_labels, void* stream) {
+  int32_t r = check_handle_batch(h, b);  // (either layout; width % 32, height % 4)
+  if (r) return r;
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES || !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "n_ranges must be 1..64");
+  if (b->width > 8192 || blob_max_labels(b->width / 4, b->height / 4) > 30000)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "frame too large for the multi-blob sensor");
+  if (b->n_frames > 0 && !targets) return fail(TRIK_IVIDTRANSCODE_EFAIL, "targets is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0) return 0;
+  r = check_device(h, b, targets);
+  if (r) return r;
+  if (b->width == 0 || b->height == 0) {
+    const size_t slots = (size_t)b->n_frames * (size_t)n;
+    HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * 8 * slots, s));
+    if (top) HIP_TRY(hipMemsetAsync(top, 0, sizeof(int32_t) * 24 * slots, s));
+    if (n_labels) HIP_TRY(hipMemsetAsync(n_labels, 0, sizeof(int32_t) * slots, s));
+    return 0;
+  }
+  return blob_ranges_core(h, *b, ranges, n, targets, top, meta, labels, n_labels, s);
+}
+
+// BMB:110-130 on the host: the centre/tolerance range in the from/to form
+extern "C" int32_t trik_hsv_blob_range_of(const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg* hsv,
+                                          TRIK_VIDTRANSCODE_CV_InArgsAlg* out) {
+  if (!hsv || !out) return fail(TRIK_IVIDTRANSCODE_EFAIL, "blob_range_of: NULL argument");
+  *out = blob_range_args(*hsv);
+  return 0;
+}
+
 extern "C" int32_t trik_hsv_blob_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
                                          const uint8_t* meta, const int32_t* top, int32_t out_width,
                                          int32_t out_height, int32_t out_line_length, uint8_t* previews,

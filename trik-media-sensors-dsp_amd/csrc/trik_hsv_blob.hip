@@ -7,6 +7,11 @@
 //                    metapixel (BMB:171-190); set when more than 2 of 16
 //                    (CLU:185-186).  A lane per (metapixel, row of it): four
 //                    lanes sum with two xor-shuffles.
+//  blob_meta_ranges_kernel  the same pass for a group of up to 4 ranges from
+//                    one read of ov7670 or packed-YUYV frames, the ranges'
+//                    counts side by side in the byte lanes of one register
+//                    (trik_hsv_blob_batch_ranges; the clusterer then runs
+//                    over (frame, range) slots as if they were frames).
 //  blob_ccl_kernel   Clusterizer::run + postProcessing + the target epilogue,
 //                    one wave per frame, reproducing the reference's
 //                    sequential scan exactly:
@@ -113,6 +118,95 @@ void blob_meta_kernel(BlobArgs a, MetaGeom g) {
     cnt += __shfl_xor(cnt, 1, 64);
     cnt += __shfl_xor(cnt, 2, 64);
     if (rr == 0 && valid) a.meta[m] = cnt > 2 ? 1 : 0;  // (f, mr, mc) is m itself
+  }
+}
+
+// The same pass for one group of up to 4 ranges from one read of the frames
+// (trik_hsv_blob_batch_ranges): a.tables is the group's StripeTables image,
+// combine() gives range k's flag in bit 8k, so the four byte lanes of cnt count
+// the four ranges side by side (0..16 each: no carry crosses a lane).  Range
+// range0 + k of frame f writes the bitmap of slot f * n_ranges + range0 + k;
+// ranges past `live` (the last group) write nothing.  YUYV frames: one 8-byte
+// load per lane, the two words of four pixels.
+struct RangeGroup {
+  int32_t n_ranges;  // T: the bitmaps of one frame
+  int32_t range0;    // this group's first range
+  int32_t live;      // its ranges, 1..4
+};
+template <int LAYOUT>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8)))
+void blob_meta_ranges_kernel(BlobArgs a, MetaGeom g, RangeGroup rg) {
+  {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4* src = reinterpret_cast<const u32x4*>(a.tables);
+    typedef __attribute__((address_space(3))) u32x4* lds_u128_wptr;
+    lds_u128_wptr dst = (lds_u128_wptr)(uintptr_t)0;
+    for (int i = threadIdx.x; i < (int)(sizeof(StripeTables) / 16); i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  const uint32_t hue_lane = (uint32_t)offsetof(StripeTables, hue) + ((t % kHueCopies) << 2);
+  const uint32_t m43_lane = (uint32_t)offsetof(StripeTables, m43) + ((t % kM43Copies) << 2);
+  const int rr = t & 3;
+  const uint32_t bw = g.per_row.d;
+  const int64_t ll = a.line_length;
+  for (uint32_t base = blockIdx.x * 256u; base < g.total; base += gridDim.x * 256u) {
+    const uint32_t m = base + (uint32_t)(t >> 2);
+    const bool valid = m < g.total;
+    uint32_t cnt = 0, out = 0;
+    if (valid) {
+      const uint32_t f = fdiv(m, g.per_frame), rem = m - f * g.per_frame.d;
+      const uint32_t mr = fdiv(rem, g.per_row), mc = rem - mr * bw;
+      const uint8_t* row = a.frames + (int64_t)f * a.frame_stride + (int64_t)(4 * mr + rr) * ll;
+      uint32_t w0, w1;
+      if (LAYOUT == TRIK_HSV_LAYOUT_YUYV) {
+        const uint8_t* p = row + 8 * mc;
+        if (a.aligned4) {
+          typedef uint32_t u32x2 __attribute__((ext_vector_type(2), aligned(4)));
+          const u32x2 v = *reinterpret_cast<const u32x2*>(p);
+          w0 = v.x;
+          w1 = v.y;
+        } else {
+          w0 = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+          w1 = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
+        }
+      } else {
+        const uint8_t* yp = row + 4 * mc;
+        const uint8_t* cp = yp + (int64_t)a.height * ll;
+        uint32_t yy, cc;
+        if (a.aligned4) {
+          yy = *reinterpret_cast<const uint32_t*>(yp);
+          cc = *reinterpret_cast<const uint32_t*>(cp);
+        } else {
+          yy = (uint32_t)yp[0] | ((uint32_t)yp[1] << 8) | ((uint32_t)yp[2] << 16) | ((uint32_t)yp[3] << 24);
+          cc = (uint32_t)cp[0] | ((uint32_t)cp[1] << 8) | ((uint32_t)cp[2] << 16) | ((uint32_t)cp[3] << 24);
+        }
+        ov7670_words(yy, cc, w0, w1);
+      }
+      Phase1 p[4];
+      p[0] = phase1<0>(w0, w0 ^ 0xFF00FF00u, m43_lane);
+      p[1] = phase1<1>(w0, w0 ^ 0xFF00FF00u, m43_lane);
+      p[2] = phase1<0>(w1, w1 ^ 0xFF00FF00u, m43_lane);
+      p[3] = phase1<1>(w1, w1 ^ 0xFF00FF00u, m43_lane);
+      uint32_t mm[4], sv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        mm[j] = lds_u32(p[j].m43_addr);
+        sv[j] = lds_u8(p[j].sv_addr);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        cnt += combine(lds_u32(phase2_addr(mm[j], p[j], hue_lane)), sv[j]) & 0x01010101u;
+      // slot (f, range0)'s bitmap, this metapixel (below 2^31: launch_blob_meta_ranges)
+      out = (f * (uint32_t)rg.n_ranges + (uint32_t)rg.range0) * g.per_frame.d + rem;
+    }
+    cnt += __shfl_xor(cnt, 1, 64);
+    cnt += __shfl_xor(cnt, 2, 64);
+    if (rr == 0 && valid) {
+#pragma unroll
+      for (int k = 0; k < kRangesPerLaunch; ++k)
+        if (k < rg.live) a.meta[out + (uint32_t)k * g.per_frame.d] = ((cnt >> (8 * k)) & 0xFFu) > 2 ? 1 : 0;
+    }
   }
 }
 
@@ -617,6 +711,38 @@ int launch_blob(const BlobArgs& a, hipStream_t s) {
   };
   auto kern = b.meta_lds ? pick(std::true_type{}) : pick(std::false_type{});
   hipLaunchKernelGGL(kern, dim3((unsigned)a.n_frames), dim3(64), lds, s, b);
+  return hipGetLastError();
+}
+
+int launch_blob_meta_ranges(const BlobArgs& a, int layout, int n_ranges, int range0, int live, hipStream_t s) {
+  if (a.n_frames <= 0 || a.width <= 0 || a.height <= 0) return hipSuccess;
+  const int bw = a.width >> 2, bh = a.height >> 2;
+  const int64_t total = (int64_t)a.n_frames * bw * bh;
+  // every bitmap index of the launch fits 31 bits, the metapixel index too
+  if (total * n_ranges >= (1ll << 31) || !a.tables || !a.meta || live < 1 || live > kRangesPerLaunch ||
+      range0 < 0 || range0 + live > n_ranges)
+    return hipErrorInvalidValue;
+  if (total == 0) return hipSuccess;
+  const bool yuyv = layout == TRIK_HSV_LAYOUT_YUYV;
+  const void* kern = yuyv ? reinterpret_cast<const void*>(blob_meta_ranges_kernel<TRIK_HSV_LAYOUT_YUYV>)
+                          : reinterpret_cast<const void*>(blob_meta_ranges_kernel<TRIK_HSV_LAYOUT_OV7670>);
+  {
+    hipError_t e = set_dynamic_lds(kern, (int)sizeof(StripeTables));
+    if (e != hipSuccess) return e;
+  }
+  MetaGeom g;
+  g.per_frame = make_div((uint32_t)(bw * bh));
+  g.per_row = make_div((uint32_t)bw);
+  g.total = (uint32_t)total;
+  const RangeGroup rg = {n_ranges, range0, live};
+  const int64_t chunks = (total + 255) / 256, slots = 2LL * device_cus();
+  const dim3 grid((unsigned)(chunks < slots ? chunks : slots));
+  if (yuyv)
+    hipLaunchKernelGGL(blob_meta_ranges_kernel<TRIK_HSV_LAYOUT_YUYV>, grid, dim3(1024), sizeof(StripeTables), s, a, g,
+                       rg);
+  else
+    hipLaunchKernelGGL(blob_meta_ranges_kernel<TRIK_HSV_LAYOUT_OV7670>, grid, dim3(1024), sizeof(StripeTables), s, a,
+                       g, rg);
   return hipGetLastError();
 }
 

@@ -410,6 +410,11 @@ int32_t line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
 int32_t blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
                   TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,
                   hipStream_t s, BlobArgs& ba);
+// the same for n_ranges ranges per frame, on either layout; outputs by slot
+// (frame * n_ranges + range), in chunks of TRIK_HSV_BLOB_CHUNK_SLOTS slots
+int32_t blob_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges,
+                         int n_ranges, TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels,
+                         int32_t* n_labels, hipStream_t s);
 // its preview: set metapixels, guide lines, target marks
 int32_t blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta, const int32_t* top,
                           int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);

@@ -427,6 +427,12 @@ int launch_blob(const BlobArgs& a, hipStream_t s);
 // launch_blob with a.meta_from_chroma set then runs only the clusterer.
 bool blob_chroma_ok(const BlobArgs& a);
 int launch_blob_meta_chroma(const BlobArgs& a, const ChromaTables* ct, const RangeTables* rt, hipStream_t s);
+// The metapixel bitmaps of one group of `live` <= 4 ranges (a.tables: the
+// group's StripeTables) for a.n_frames frames of `layout`, from one read of
+// the frames (trik_hsv_blob_batch_ranges): range range0 + k of frame f goes to
+// a.meta + (f * n_ranges + range0 + k) * bw * bh.  launch_blob with meta_ready
+// set and n_frames = the slot count then runs the clusterer over the slots.
+int launch_blob_meta_ranges(const BlobArgs& a, int layout, int n_ranges, int range0, int live, hipStream_t s);
 // guide lines + a 3x3 mark per kept target (OSEQ:548-580), from BlobArgs.top
 int launch_blob_overlay(const PreviewArgs& a, const int32_t* top, hipStream_t s);
 

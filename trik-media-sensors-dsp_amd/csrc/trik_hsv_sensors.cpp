@@ -374,6 +374,78 @@ int32_t trik_hsv::blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
   return note_uses(h, set, false, s, &h->blob_users);
 }
 
+// The multi-blob sensor for n_ranges ranges per frame.  A slot is one (frame,
+// range) pair, s = f * n_ranges + t; the clusterer runs over slots as if they
+// were frames.  The batch goes in chunks of whole frames of at most
+// TRIK_HSV_BLOB_CHUNK_SLOTS slots (at least one frame), so the statistics
+// scratch is that of a single-range call of as many frames.  Per chunk: one
+// bitmap launch per group of 4 ranges (each reads the chunk's frames once),
+// then one clusterer launch; all stream-ordered.
+int32_t trik_hsv::blob_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
+                                   const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int n_ranges,
+                                   TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels,
+                                   int32_t* n_labels, hipStream_t s) {
+  const int chunk_frames = TRIK_HSV_BLOB_CHUNK_SLOTS / n_ranges > 1 ? TRIK_HSV_BLOB_CHUNK_SLOTS / n_ranges : 1;
+  const int first = b.n_frames < chunk_frames ? b.n_frames : chunk_frames;
+  int32_t r = ensure_blob_scratch(h, first * n_ranges, b.width, b.height, s);
+  if (r) return r;
+  TableSet* set = nullptr;
+  r = acquire_tables(h, ranges, n_ranges, s, &set);
+  if (r) return r;
+  const int groups = (n_ranges + kRangesPerLaunch - 1) / kRangesPerLaunch;
+  const int64_t cells = (int64_t)(b.width / 4) * (b.height / 4);
+  h->pending_set = nullptr;
+  h->hot_groups.assign((size_t)groups, TRIK_HSV_HOT_STRIPE);
+  bool enqueued = false;
+  for (int f0 = 0; f0 < b.n_frames && !r; f0 += chunk_frames) {
+    const int nf = b.n_frames - f0 < chunk_frames ? b.n_frames - f0 : chunk_frames;
+    const int64_t s0 = (int64_t)f0 * n_ranges;  // the chunk's first slot
+    BlobArgs a;
+    a.frames = static_cast<const uint8_t*>(b.frames) + (f0 ? (int64_t)f0 * b.frame_stride : 0);
+    a.frame_stride = b.frame_stride;
+    a.n_frames = nf;
+    a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+    a.range = pack_range(ranges[0]);
+    a.aligned4 = aligned4(b);
+    a.meta = meta ? meta + s0 * cells : h->d_meta;
+    a.labels = labels ? labels + s0 * cells : nullptr;
+    a.stats = h->d_blob_stats;
+    a.max_labels = (int32_t)blob_max_labels(b.width / 4, b.height / 4);
+    a.targets = targets + s0 * 8;
+    a.top = top ? top + s0 * 24 : h->d_blob_top;
+    a.n_labels = n_labels ? n_labels + s0 : nullptr;
+    for (int g = 0; g < groups && !r; ++g) {
+      const int left = n_ranges - g * kRangesPerLaunch;
+      a.tables = set->d_stripe + g;
+      const int e = launch_blob_meta_ranges(a, b.layout, n_ranges, g * kRangesPerLaunch,
+                                            left < kRangesPerLaunch ? left : kRangesPerLaunch, s);
+      if (e != hipSuccess)
+        r = fail(TRIK_IVIDTRANSCODE_EFAIL,
+                 std::string("launch_blob_meta_ranges: ") + hipGetErrorString((hipError_t)e));
+      else
+        enqueued = true;
+    }
+    if (r) break;
+    a.tables = set->d_stripe;
+    a.n_frames = nf * n_ranges;
+    a.meta_ready = 1;
+    const int e = launch_blob(a, s);
+    if (e != hipSuccess) {
+      h->blob_stats_dirty = true;  // (the clusterer may not have restored its statistics to zero)
+      r = fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("launch_blob: ") + hipGetErrorString((hipError_t)e));
+    }
+  }
+  if (r) {  // what was enqueued still reads the tables and writes the scratch
+    if (enqueued) {
+      const std::string msg = last_error();
+      (void)note_uses(h, set, false, s, &h->blob_users);
+      return fail(r, msg);
+    }
+    return r;
+  }
+  return note_uses(h, set, false, s, &h->blob_users);
+}
+
 std::string trik_hsv::mxn_grid_error(int64_t rows_m, int64_t cols_n) {
   if (rows_m < 1 || cols_n < 1 || rows_m * cols_n > 100)
     return "the MxN sensor takes widthM >= 1, heightN >= 1 and widthM * heightN <= 100";

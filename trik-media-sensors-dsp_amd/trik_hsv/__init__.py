@@ -266,6 +266,33 @@ class Detector(_HotKernel):
             raise TrikHsvError(rc, "trik_hsv_blob_batch")
         return out
 
+    def blob_batch_ranges(self, frames, width, height, line_length, ranges, *, layout=LAYOUT_OV7670,
+                          n_frames=None, frame_stride=None, meta=False, labels=False, stream=None):
+        """The multi-blob sensor over N frames of either layout for T from/to
+        ranges per frame (trik_hsv_blob_batch_ranges; blob_range_of converts a
+        centre/tolerance range).  Returns blob_batch's dict with a range axis:
+        targets int8 [N, T, 8, 4], top int32 [N, T, 8, 3], n_labels int32
+        [N, T], and meta uint8 / labels int16 [N, T, H/4, W/4] when asked."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+        arr, T = _ranges(ranges)
+        dev, n = frames.device, b.n_frames
+        out = {"targets": torch.empty((n, T, 8, 4), dtype=torch.int8, device=dev),
+               "top": torch.empty((n, T, 8, 3), dtype=torch.int32, device=dev),
+               "n_labels": torch.empty((n, T), dtype=torch.int32, device=dev),
+               "meta": torch.empty((n, T, height // 4, width // 4), dtype=torch.uint8, device=dev)
+               if meta else None,
+               "labels": torch.empty((n, T, height // 4, width // 4), dtype=torch.int16, device=dev)
+               if labels else None}
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        rc = _lib.trik_hsv_blob_batch_ranges(self._h, C.byref(b), arr, T, ptr(out["targets"]), ptr(out["top"]),
+                                             ptr(out["meta"]), ptr(out["labels"]), ptr(out["n_labels"]),
+                                             _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_blob_batch_ranges")
+        return out
+
     def blob_preview(self, frames, width, height, line_length, meta, top, *, out_width=None,
                      out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
         """Multi-blob previews (uint8 [N, out_height, out_line_length]) from blob_batch's meta and top."""
@@ -527,6 +554,22 @@ def auto_range_of(kind: int, h1: int, h2: int, s1: int = 0, s2: int = 0) -> Tupl
     if rc:
         raise TrikHsvError(rc, "trik_hsv_auto_range_of")
     return tuple(int(v) for v in out)
+
+
+BLOB_CHUNK_SLOTS = _abi.BLOB_CHUNK_SLOTS  # (frame, range) slots per chunk of blob_batch_ranges
+
+
+def blob_range_of(hsv: Sequence[int]) -> Range:
+    """The from/to range blob_batch uses for hsv = (hue, hueTol, sat, satTol,
+    val, valTol) (BMB:110-130), as blob_batch_ranges and process_batch take
+    it.  trik_hsv_blob_range_of, host code."""
+    alg = _abi.OV7670InArgsAlg(1, *[int(v) for v in hsv], 0)
+    out = _abi.InArgsAlg()
+    rc = _lib.trik_hsv_blob_range_of(C.byref(alg), C.byref(out))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_blob_range_of")
+    return (out.detectHueFrom, out.detectHueTo, out.detectSatFrom, out.detectSatTo, out.detectValFrom,
+            out.detectValTo)
 
 
 def batch_targets(sums, width, height, *, stream=None):

@@ -37,6 +37,7 @@ MAX_IO_BUFFERS = 16
 LAYOUT_YUYV = 0
 LAYOUT_OV7670 = 1
 MAX_RANGES = 64
+BLOB_CHUNK_SLOTS = 4096  # TRIK_HSV_BLOB_CHUNK_SLOTS
 
 i32, i64, u8, u16, u64 = C.c_int32, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint64
 A2 = i32 * MAXOUTSTREAMS
@@ -243,6 +244,9 @@ PROTOTYPES = {
                                C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_blob_batch": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(OV7670InArgsAlg), C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_blob_batch_ranges": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(InArgsAlg), i32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_blob_range_of": ([C.POINTER(OV7670InArgsAlg), C.POINTER(InArgsAlg)], i32),
     "trik_hsv_blob_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, C.c_void_p, i32, i32, i32,
                                C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_mxn_batch": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, C.c_void_p,

@@ -789,6 +789,46 @@ int32_t trik_hsv_auto_range_of(int32_t kind, int32_t h1, int32_t h2, int32_t s1,
  * handle, another codec's handle or an unknown mode. */
 int32_t trik_hsv_set_auto_detect(TRIK_VIDTRANSCODE_CV_Handle handle, int32_t mode);
 
+/* The object sensor for N frames with HSV ranges PER FRAME, read from device
+ * memory by the kernel: one camera, one calibration per frame of the batch.
+ *   ranges_dev   [n_frames][n_ranges][6] uint16 (device): hueFrom, hueTo,
+ *                satFrom, satTo, valFrom, valTo in InArgs units (hue 0..359,
+ *                saturation and value 0..100);
+ *   sums_dev     [n_frames][n_ranges] TrikHsvTargetSums (device), zeroed by
+ *                the call;
+ *   targets_dev  the same shape of TrikHsvTarget (device), or NULL.
+ * Slot (f, t) holds exactly what trik_hsv_process_batch writes for frame f
+ * alone with the one range that holds the same six numbers, sums and targets,
+ * in both layouts and for every geometry that call takes (padded line_length,
+ * odd frame_stride, a misaligned base: those read bytes instead of words).
+ * The six numbers are scaled and packed as WSEQ:425-445 does, in int32: each
+ * bound is clamped to 0..255 after the scaling, so a saturation or value above
+ * 255 -- which an InArgs byte cannot hold -- behaves as 255.
+ * No handle: no table depends on a range, H, S and V are computed per pixel
+ * (DESIGN.md 4.10).  Stream-ordered, no host synchronisation; the host never
+ * dereferences ranges_dev, the kernel reads it when it runs, so a producer
+ * earlier on the stream (trik_hsv_ranges_of_detect, a copy) is seen.
+ * n_ranges is 1..TRIK_HSV_MAX_RANGES.  n_frames == 0 returns 0 and touches
+ * nothing; width or height 0 zeroes sums and targets.  Fails
+ * (trik_hsv_last_error()) and enqueues nothing for a NULL batch, NULL ranges
+ * or sums when n_frames > 0, an unknown layout, a geometry the other batched
+ * calls refuse, or n_ranges out of bounds. */
+int32_t trik_hsv_frame_ranges_batch(const TrikHsvFrameBatch* batch, const uint16_t* ranges_dev, int32_t n_ranges,
+                                    TrikHsvTargetSums* sums_dev, TrikHsvTarget* targets_dev, void* hip_stream);
+
+/* The closed loop on the device: detect_dev [n][6] uint16 (hue, hueTol, sat,
+ * satTol, val, valTol, as trik_hsv_batch_auto_range and _auto_range_exact
+ * write them) -> the from/to six-tuple of frame i at ranges_dev +
+ * (i * n_ranges + t) * 6, by the rule of cv_bitmap_builder_reference.hpp:
+ * 110-130 in int arithmetic: hue from/to = (hue -/+ tol) mod 360, saturation
+ * and value from/to = centre -/+ tol clipped to 0..100.  For inputs that fit
+ * TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg the result equals
+ * trik_hsv_blob_range_of.  The other entries of ranges_dev are left as they
+ * are.  Fails for a NULL buffer when n > 0, n < 0, n_ranges outside
+ * 1..TRIK_HSV_MAX_RANGES or t outside 0..n_ranges-1. */
+int32_t trik_hsv_ranges_of_detect(const uint16_t* detect_dev, int32_t n, uint16_t* ranges_dev, int32_t n_ranges,
+                                  int32_t t, void* hip_stream);
+
 /* The line sensor for N ov7670 frames: sums_dev[i] =
  * {points, sum_x, cross points} -- cross points in the sum_y slot -- for V in
  * [val_from, val_to] (InArgs percent units) in columns 5..W-5, cross points

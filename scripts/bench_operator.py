@@ -33,6 +33,11 @@
               four SURVEY 8(d) ranges over 4096 x 640x480 ov7670 scene frames in
               one call, against four trik_hsv_blob_batch calls, alternating; and
               the one call on the packed-YUYV twins of the same frames.
+  frame_ranges (--frame-ranges, a run of its own) trik_hsv_frame_ranges_batch:
+              4096 x 640x480 YUYV scene frames, each under its own ranges read
+              from device memory, T = 4 and T = 1, beside trik_hsv_process_batch
+              with one shared set; and at N = 256 against a loop of 256
+              single-frame trik_hsv_process_batch calls with 256 range sets.
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -130,6 +135,83 @@ def blob_ranges(args):
                 "per chunk of 4096 slots; medians of alternating rounds"}}
 
 
+def frame_ranges(args):
+    """trik_hsv_frame_ranges_batch (HSV ranges per frame, read on the device)
+    on 640x480 YUYV scene frames, alternating in this process with
+      (a) trik_hsv_process_batch with ONE shared set at the same N and T, and
+      (b) at N = 256, a loop of 256 single-frame trik_hsv_process_batch calls
+          with 256 different range sets (each call builds its tables) -- the
+          only way to per-frame ranges without the new call.
+    Algorithmic bytes = the frames once (2 B/px)."""
+    import torch
+
+    import trik_hsv
+
+    W, H, LL, F, FB = 640, 480, 1280, args.frames, 256
+    base = [(0, 30, 50, 100, 30, 100), (90, 150, 40, 100, 20, 100), (200, 260, 40, 100, 20, 100),
+            (330, 20, 30, 100, 30, 100)]  # T0-T3
+
+    def sets(n, t):  # frame f: the base ranges with every hue bound shifted by f degrees
+        return [[((hf + f) % 360, (ht + f) % 360, sf, st, vf, vt) for hf, ht, sf, st, vf, vt in base[:t]]
+                for f in range(n)]
+
+    fb = H * LL
+    dev = torch.empty(F * fb, dtype=torch.uint8, device="cuda")
+    trik_hsv.synth(dev, W, H, LL, trik_hsv.LAYOUT_YUYV, 1, 0x7A1C)
+    stream = torch.cuda.current_stream()
+    det = trik_hsv.Detector()
+    dev_sets = {t: torch.tensor(sets(F, t), dtype=torch.int16, device="cuda") for t in (4, 1)}
+    small_sets = sets(FB, 4)
+    small_dev = torch.tensor(small_sets, dtype=torch.int16, device="cuda")
+    assert len({tuple(s) for s in small_sets}) == FB
+
+    def loop256():
+        return [det.process_batch(dev[f * fb:(f + 1) * fb], W, H, LL, trik_hsv.LAYOUT_YUYV, small_sets[f])
+                for f in range(FB)]
+
+    fns = {
+        "frame_ranges_T4": lambda: trik_hsv.frame_ranges_batch(dev, W, H, LL, trik_hsv.LAYOUT_YUYV, dev_sets[4]),
+        "shared_T4": lambda: det.process_batch(dev, W, H, LL, trik_hsv.LAYOUT_YUYV, base),
+        "frame_ranges_T1": lambda: trik_hsv.frame_ranges_batch(dev, W, H, LL, trik_hsv.LAYOUT_YUYV, dev_sets[1]),
+        "shared_T1": lambda: det.process_batch(dev, W, H, LL, trik_hsv.LAYOUT_YUYV, base[:1]),
+        "frame_ranges_256_T4": lambda: trik_hsv.frame_ranges_batch(dev, W, H, LL, trik_hsv.LAYOUT_YUYV, small_dev,
+                                                                   n_frames=FB),
+        "loop_256_T4": loop256,
+    }
+    one, singles = fns["frame_ranges_256_T4"](), loop256()
+    same = all(torch.equal(one[0][f], singles[f][0][0]) and torch.equal(one[1][f], singles[f][1][0])
+               for f in range(FB))
+    # frame 0's set is the shared set: its slots must agree with the shared-range step
+    same0 = torch.equal(fns["frame_ranges_T4"]()[0][0], fns["shared_T4"]()[0][0])
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name, fn in fns.items():
+            runs[name].append(timed(fn, stream, 2 if name == "loop_256_T4" else args.iters))
+    det.close()
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name, n):
+        nb = n * fb
+        return {"frames": n, "ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]],
+                "Mframes_per_s": round(n / med[name] / 1e3, 3), "bytes_algorithmic": nb,
+                "achieved_GBs": round(nb / (med[name] / 1e3) / 1e9, 1),
+                "hbm_frac": round(nb / (med[name] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+    out = {k: row(k, FB if "256" in k else F) for k in fns}
+    for t in (4, 1):
+        out[f"frame_ranges_T{t}"]["over_shared"] = round(med[f"frame_ranges_T{t}"] / med[f"shared_T{t}"], 2)
+    out["frame_ranges_256_T4"]["over_loop"] = round(med["frame_ranges_256_T4"] / med["loop_256_T4"], 4)
+    out["loop_256_T4"]["ms_per_call"] = round(med["loop_256_T4"] / FB, 4)
+    return {"frame_ranges": {
+        "geometry": [W, H], "layout": "YUYV", "scene_frames": True, "iters": args.iters, "rounds": args.rounds,
+        "results_identical_256": bool(same), "frame0_equals_shared": bool(same0), **out,
+        "note": "frame_ranges_*: memset + frame_ranges_kernel (exact per-pixel HSV, ranges read from device memory, "
+                "frame f under the base ranges shifted by f degrees of hue) + targets_kernel; shared_*: "
+                "trik_hsv_process_batch, one set for the batch (warm tables); loop_256_T4: 256 single-frame "
+                "trik_hsv_process_batch calls, 256 different sets (2 timed iterations per round); medians of "
+                "alternating rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -140,9 +222,15 @@ def main():
                     help="stop after the preview, auto_range, line and autorange_exact rows")
     ap.add_argument("--blob-ranges", action="store_true",
                     help="the blob_ranges mode alone: one 4-range multi-blob call against four single-range calls")
+    ap.add_argument("--frame-ranges", action="store_true",
+                    help="the frame_ranges mode alone: per-frame ranges against the shared-range step and against a "
+                         "loop of single-frame calls")
     args = ap.parse_args()
     if args.blob_ranges:
         print(json.dumps(blob_ranges(args)))
+        return
+    if args.frame_ranges:
+        print(json.dumps(frame_ranges(args)))
         return
     import numpy as np
     import torch

@@ -267,6 +267,37 @@ extern "C" int32_t trik_hsv_line_batch(const TrikHsvFrameBatch* b, int32_t val_f
   return 0;
 }
 
+extern "C" int32_t trik_hsv_frame_ranges_batch(const TrikHsvFrameBatch* b, const uint16_t* ranges, int32_t n,
+                                               TrikHsvTargetSums* sums, TrikHsvTarget* targets, void* stream) {
+  int32_t rc = check_batch(b);
+  if (rc) return rc;
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES) return fail(TRIK_IVIDTRANSCODE_EFAIL, "n_ranges must be 1..64");
+  if (b->n_frames > 0 && !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges is NULL");
+  if (b->n_frames > 0 && !sums) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (b->n_frames == 0) return 0;
+  const size_t slots = (size_t)b->n_frames * (size_t)n;
+  HIP_TRY(hipMemsetAsync(sums, 0, sizeof(TrikHsvTargetSums) * slots, s));
+  if (b->width == 0 || b->height == 0) {
+    if (targets) HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * slots, s));
+    return 0;
+  }
+  HIP_TRY(launch_frame_ranges(*b, ranges, n, sums, s));
+  if (targets) HIP_TRY(launch_targets(*b, n, sums, targets, s));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_ranges_of_detect(const uint16_t* detect, int32_t n, uint16_t* ranges, int32_t n_ranges,
+                                             int32_t t, void* stream) {
+  if (n < 0) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges_of_detect: n < 0");
+  if (n_ranges < 1 || n_ranges > TRIK_HSV_MAX_RANGES)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges_of_detect: n_ranges must be 1..64");
+  if (t < 0 || t >= n_ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges_of_detect: t must be 0..n_ranges-1");
+  if (n > 0 && (!detect || !ranges)) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges_of_detect: NULL buffer");
+  HIP_TRY(launch_ranges_of_detect(detect, n, ranges, n_ranges, t, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
 extern "C" int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
                                          int32_t val_from, int32_t val_to, const TrikHsvTargetSums* sums,
                                          int32_t out_width, int32_t out_height, int32_t out_line_length,

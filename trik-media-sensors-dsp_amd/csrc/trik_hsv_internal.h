@@ -106,7 +106,34 @@ struct alignas(16) ChromaTables {
   unsigned long long flagged_words;
 };
 
-PackedRange pack_range(const TRIK_VIDTRANSCODE_CV_InArgsAlg& r);
+// WSEQ:425-445 on the six InArgs numbers as int32 (hue 0..359, saturation and
+// value 0..100, each scaled to 0..255 and clamped; stdcpp.hpp:38-44): the one
+// definition, for the host's table compiler and for the kernel that packs the
+// ranges it reads from device memory (trik_hsv_frame_ranges.hip).
+__host__ __device__ inline uint32_t pack_scale(int32_t v, int32_t full) {
+  const int32_t x = (v * 255) / full;
+  return (uint32_t)(x < 0 ? 0 : (x > 255 ? 255 : x));
+}
+__host__ __device__ inline PackedRange pack_range(int32_t hue_from, int32_t hue_to, int32_t sat_from, int32_t sat_to,
+                                                  int32_t val_from, int32_t val_to) {
+  const uint32_t hf = pack_scale(hue_from, 359), ht = pack_scale(hue_to, 359);
+  const uint32_t sf = pack_scale(sat_from, 100), st = pack_scale(sat_to, 100);
+  const uint32_t vf = pack_scale(val_from, 100), vt = pack_scale(val_to, 100);
+  PackedRange p;
+  if (hf <= ht) {
+    p.from = (vf << 16) | (sf << 8) | hf;
+    p.to = (vt << 16) | (st << 8) | ht;
+    p.expect = 0;
+  } else {  // hue wrap through 0
+    p.from = (vf << 16) | (sf << 8) | ((ht + 1) & 0xFF);
+    p.to = (vt << 16) | (st << 8) | ((hf - 1) & 0xFF);
+    p.expect = 1;
+  }
+  return p;
+}
+inline PackedRange pack_range(const TRIK_VIDTRANSCODE_CV_InArgsAlg& r) {
+  return pack_range(r.detectHueFrom, r.detectHueTo, r.detectSatFrom, r.detectSatTo, r.detectValFrom, r.detectValTo);
+}
 void compile_tables(const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges, int n, RangeTables* out);
 // compile_tables in two parts: the head (LUTs, per-value H/S/V tests) first,
 // then the sat/val table (which reads the head's lut255)
@@ -372,6 +399,13 @@ int launch_targets(const TrikHsvFrameBatch& b, int n_ranges, const TrikHsvTarget
                    TrikHsvTarget* targets, hipStream_t s);
 int launch_synth(const TrikHsvFrameBatch& b, uint8_t* frames, int first_frame, int kind,
                  uint64_t seed, hipStream_t s);
+// HSV ranges per frame, read on the device (trik_hsv_frame_ranges.hip): adds
+// into sums[f][t] (zeroed by the caller) the sums of frame f under
+// ranges[f][t][6]; b validated, with n_frames, width and height > 0.
+int launch_frame_ranges(const TrikHsvFrameBatch& b, const uint16_t* ranges, int n_ranges, TrikHsvTargetSums* sums,
+                        hipStream_t s);
+// detect[i][6] (centre, tolerance) -> ranges[i][n_ranges][6]'s entry t (BMB:110-130)
+int launch_ranges_of_detect(const uint16_t* detect, int n, uint16_t* ranges, int n_ranges, int t, hipStream_t s);
 // preview_kernel then overlay_kernel (circle from sums[f * sums_pitch])
 int launch_preview(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
 int launch_auto_range(const AutoRangeArgs& a, hipStream_t s);

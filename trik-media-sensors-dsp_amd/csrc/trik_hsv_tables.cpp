@@ -14,29 +14,8 @@
 
 namespace trik_hsv {
 
-static inline int32_t clamp_range(int32_t lo, int32_t v, int32_t hi) {  // stdcpp.hpp:38-44
-  return v < lo ? lo : (v > hi ? hi : v);
-}
-
-PackedRange pack_range(const TRIK_VIDTRANSCODE_CV_InArgsAlg& r) {  // WSEQ:425-445
-  const uint32_t hf = (uint32_t)clamp_range(0, ((int32_t)r.detectHueFrom * 255) / 359, 255);
-  const uint32_t ht = (uint32_t)clamp_range(0, ((int32_t)r.detectHueTo * 255) / 359, 255);
-  const uint32_t sf = (uint32_t)clamp_range(0, ((int32_t)r.detectSatFrom * 255) / 100, 255);
-  const uint32_t st = (uint32_t)clamp_range(0, ((int32_t)r.detectSatTo * 255) / 100, 255);
-  const uint32_t vf = (uint32_t)clamp_range(0, ((int32_t)r.detectValFrom * 255) / 100, 255);
-  const uint32_t vt = (uint32_t)clamp_range(0, ((int32_t)r.detectValTo * 255) / 100, 255);
-  PackedRange p;
-  if (hf <= ht) {
-    p.from = (vf << 16) | (sf << 8) | hf;
-    p.to = (vt << 16) | (st << 8) | ht;
-    p.expect = 0;
-  } else {  // hue wrap through 0
-    p.from = (vf << 16) | (sf << 8) | ((ht + 1) & 0xFF);
-    p.to = (vt << 16) | (st << 8) | ((hf - 1) & 0xFF);
-    p.expect = 1;
-  }
-  return p;
-}
+// (pack_range, WSEQ:425-445, is trik_hsv_internal.h's: the kernel that reads
+// its ranges from device memory packs them with the same code)
 
 static inline bool outside(uint32_t x, uint32_t lo, uint32_t hi) { return x < lo || x > hi; }
 

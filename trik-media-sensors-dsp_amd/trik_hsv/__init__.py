@@ -437,6 +437,64 @@ def line_batch(frames, width, height, line_length, val_from, val_to, *, band=Non
     return sums, targets
 
 
+def frame_ranges_batch(frames, width, height, line_length, layout, ranges, *, n_frames=None, frame_stride=None,
+                       stream=None, sums=None, targets=None):
+    """The object sensor with HSV ranges per frame (trik_hsv_frame_ranges_batch):
+    returns (sums int64 [N,T,3], targets int8 [N,T,4]) as process_batch does,
+    frame f under ranges[f].  `ranges` is a CUDA tensor [N,T,6] of int16 /
+    uint16 (hue_from, hue_to, sat_from, sat_to, val_from, val_to), read by the
+    kernel in stream order, or a host sequence [N][T][6], uploaded on the
+    stream."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+    s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+    if not isinstance(ranges, torch.Tensor):
+        host = torch.tensor(ranges, dtype=torch.int32).to(torch.int16)  # (uint16 bits)
+        host = host.reshape(0, 1, 6) if host.numel() == 0 else host
+        with torch.cuda.stream(s):
+            ranges = host.pin_memory().to(frames.device, non_blocking=True)
+    if (not ranges.is_cuda or ranges.dtype.itemsize != 2 or ranges.dtype.is_floating_point or ranges.dim() != 3
+            or ranges.shape[0] != b.n_frames or ranges.shape[2] != 6 or not ranges.is_contiguous()):
+        raise ValueError("ranges must be a contiguous CUDA (HIP) tensor [n_frames, T, 6] of int16 or uint16")
+    T = ranges.shape[1]
+    if sums is None:
+        sums = torch.empty((b.n_frames, T, 3), dtype=torch.int64, device=frames.device)
+    if targets is None:
+        targets = torch.empty((b.n_frames, T, 4), dtype=torch.int8, device=frames.device)
+    rc = _lib.trik_hsv_frame_ranges_batch(C.byref(b), C.c_void_p(ranges.data_ptr()), T, C.c_void_p(sums.data_ptr()),
+                                          C.c_void_p(targets.data_ptr()), C.c_void_p(s.cuda_stream))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_frame_ranges_batch")
+    return sums, targets
+
+
+def ranges_of_detect(detect, *, ranges=None, n_ranges=1, t=0, stream=None):
+    """detect [N,6] (hue, hueTol, sat, satTol, val, valTol: batch_auto_range's
+    or batch_auto_range_exact's output, on the device) -> entry t of each
+    frame's ranges, from/to form (trik_hsv_ranges_of_detect).  Returns the
+    ranges tensor int16 [N, n_ranges, 6]: `ranges`, or a new one (zeros but for
+    entry t)."""
+    import torch
+
+    if not detect.is_cuda or detect.dtype.itemsize != 2 or detect.dim() != 2 or detect.shape[1] != 6 \
+            or not detect.is_contiguous():
+        raise ValueError("detect must be a contiguous CUDA (HIP) tensor [N, 6] of int16 or uint16")
+    n = detect.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(detect.device)
+    if ranges is None:
+        with torch.cuda.stream(s):
+            ranges = torch.zeros((n, n_ranges, 6), dtype=torch.int16, device=detect.device)
+    elif (not ranges.is_cuda or ranges.dtype.itemsize != 2 or ranges.dim() != 3 or ranges.shape[0] != n
+          or ranges.shape[2] != 6 or not ranges.is_contiguous()):
+        raise ValueError("ranges must be a contiguous CUDA (HIP) tensor [N, T, 6] of int16 or uint16")
+    rc = _lib.trik_hsv_ranges_of_detect(C.c_void_p(detect.data_ptr()), n, C.c_void_p(ranges.data_ptr()),
+                                        ranges.shape[1], int(t), C.c_void_p(s.cuda_stream))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_ranges_of_detect")
+    return ranges
+
+
 def edge_batch(frames, width, height, line_length, threshold=50, *, edges=False, n_frames=None,
                frame_stride=None, stream=None):
     """The ov7670 edge-line sensor over N frames (ESEQ:154-205, 397-417): sums

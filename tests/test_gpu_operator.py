@@ -188,14 +188,18 @@ def test_batch_auto_range_fallback_kernels(hsv, oracle_mod, w, h, ll, layout, n,
     assert got.tolist() == _auto_want(oracle_mod, host, fb, n, w, h, ll, layout)
 
 
-def test_batch_auto_range_single_colour_frames(hsv, table):
+@pytest.mark.parametrize("offset", [0, 4])
+def test_batch_auto_range_single_colour_frames(hsv, table, offset):
     """Every (U, V) at six Y levels, one colour per frame (96x24, a 7x7 zone,
     393,216 frames): each channel's winner is the colour's own H, S and V, so
     the output is (H x 1.4, S x 0.39, V x 0.39) with the reference's float
-    constants (hpp:190-195) -- the chunked kernel's packed two-pixel HSV
-    (hsv_key2: both pixels of a word in 16-bit halves, the B channel's 16-bit
-    wrap) against the oracle's table on every one of those (Y, U, V).  H is
-    checked exactly (1.4 H is injective), S and V through the scaling."""
+    constants (hpp:190-195) -- against the oracle's table on every one of
+    those (Y, U, V).  Offset 0: the chunked kernel's packed two-pixel HSV
+    (hsv_pair: both pixels of a word in 16-bit halves, the B channel's 16-bit
+    wrap).  Offset 4 (the frames 4 bytes past a 16-byte boundary, as in
+    test_batch_auto_range_fallback_kernels): auto_range_kernel<256> and its
+    per-pixel hsv_bytes, the word form of trik_hsv_stripe_px.h.  H is checked
+    exactly (1.4 H is injective), S and V through the scaling."""
     import torch
 
     w, h, ll = 96, 24, 192
@@ -207,7 +211,10 @@ def test_batch_auto_range_single_colour_frames(hsv, table):
     word = Y | (U << 8) | (Y << 16) | (V << 24)
     word = np.where(word >= 1 << 31, word - (1 << 32), word).astype(np.int32)
     n, per = word.size, h * ll // 4
-    dev = torch.from_numpy(word).cuda().view(-1, 1).expand(n, per).contiguous().view(torch.uint8).reshape(-1)
+    raw = torch.empty(n * per * 4 + 16, dtype=torch.uint8, device="cuda")
+    dev = raw[offset:offset + n * per * 4]
+    assert dev.data_ptr() % 16 == offset
+    dev.view(torch.int32).view(n, per).copy_(torch.from_numpy(word).cuda().view(-1, 1).expand(n, per))
     got = hsv.batch_auto_range(dev, w, h, ll, LAYOUT_YUYV).cpu().numpy().astype(np.int64)
     e = table[Y | (U << 8) | (V << 16)] & 0xFFFFFFFF
     H, S, Vv = e & 0xFF, (e >> 8) & 0xFF, (e >> 16) & 0xFF

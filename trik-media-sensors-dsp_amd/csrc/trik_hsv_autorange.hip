@@ -35,8 +35,6 @@ namespace trik_hsv {
 
 namespace {
 
-__constant__ Luts c_auto_luts = make_luts();  // trik_hsv_pixel.h
-
 constexpr int kAutoBlock = 256;
 
 // The histogram bin of pixel (row, col): (H >> 3) * 32 + (S >> 3) for the
@@ -72,10 +70,7 @@ __global__ __launch_bounds__(kAutoBlock) void auto_exact_kernel(AutoExactArgs a)
     last_col[i] = -1;
     rneg[i] = 0;
   }
-  for (int i = tid; i < 256; i += kAutoBlock) {
-    l43[i] = c_auto_luts.l43[i];
-    l255[i] = c_auto_luts.l255[i];
-  }
+  stage_luts(l43, l255, tid, kAutoBlock);
   if (tid == 0) {
     top = 0;
     start_cell[0] = 0;

@@ -236,25 +236,22 @@ __device__ __forceinline__ uint32_t chroma_of(uint32_t w) { return __builtin_amd
 __device__ __forceinline__ uint32_t chroma_of8(uint32_t w) { return __builtin_amdgcn_perm(w, w, 0x0C03010Cu); }
 
 // The exact mask (bit t = range t) of pixel PIX of YUYV word w: the stripe
-// kernel's arithmetic (trik_hsv_stripe_px.h: WSEQ:181-249 via v_dot4, the
-// 16-bit wrap in v_bfe) with LUT43/LUT255 and the H, S, V tests from LDS.
+// kernel's arithmetic (trik_hsv_stripe_px.h: rgb, WSEQ:181-249) with
+// LUT43/LUT255 and the H, S, V tests from LDS by absolute address.
 template <int PIX>
 __device__ __forceinline__ uint32_t exact_mask(uint32_t w) {
-  constexpr uint32_t kY = PIX == 0 ? 74u : (74u << 16);
-  const uint32_t wc = w ^ 0xFF00FF00u;
-  const int r = stripe_px::clamp8_shift6(__builtin_amdgcn_udot4(w, kY | (102u << 24), (uint32_t)-14248, false));
-  const int g = stripe_px::clamp8_shift6(
-      __builtin_amdgcn_udot4(wc, kY | (25u << 8) | (52u << 24), (uint32_t)-10939, false));
-  const int b = stripe_px::clamp8_shift6(__builtin_amdgcn_udot4(w, kY | (129u << 8), (uint32_t)-17672, false));
-  const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
+  const PixelRgb p = stripe_px::rgb<PIX>(w, w ^ 0xFF00FF00u);
+  const int mx = max(p.r, max(p.g, p.b)), mn = min(p.r, min(p.g, p.b));
   const uint32_t d = (uint32_t)(mx - mn);
   const int m = (int)ld16(kLdsLut43 + 2u * d);
   const uint32_t S = (ld16(kLdsLut255 + 2u * (uint32_t)mx) * d) >> 8;
-  // hue case select as in stripe_px::phase1 (G > B > R on ties), branch-free
-  const bool eqG = mx == g, eqB = mx == b;
-  const int dR = g - b, dG = b - r, dB = r - g;
+  // stripe_px::hue_case's select, kept in this kernel's own nested form: the
+  // compiler's code follows the way it is written, and through hue_case the
+  // chroma kernels come out 10 to 70 instructions longer
+  const bool eqG = mx == p.g, eqB = mx == p.b;
+  const int dR = p.g - p.b, dG = p.b - p.r, dB = p.r - p.g;
   const int diff = eqG ? dG : (eqB ? dB : dR);
-  const int base = eqG ? 21845 : (eqB ? 43690 : 0);
+  const int base = eqG ? kHueBaseG : (eqB ? kHueBaseB : 0);
   const uint32_t H = ((uint32_t)(base + m * diff) >> 8) & 0xFFu;
   return ld8(kLdsHue + H) & ld8(kLdsSat + S) & ld8(kLdsVal + (uint32_t)mx);
 }
@@ -709,8 +706,6 @@ __device__ __forceinline__ void load_chunk(const uint8_t* p, const uint8_t* pb, 
   }
 }
 
-__device__ __forceinline__ uint32_t pack_bits(uint32_t e) { return ((e * 0x01020408u) >> 24) & 0xFu; }
-
 // Per-lane sums of the exception pixels a lane drained: EN byte-packed counts
 // (range t in byte t), SX/SY 16-bit fields (ranges 0,2 | 1,3) of x and of the
 // row relative to the tile's first row; unpacked into 32-bit per-range sums
@@ -1025,8 +1020,8 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
           if (MASKS && (i < 4 ? valid : validb)) {  // verification mode: the exact path writes the flagged pixels
             const int y = y0 + s * g.rstep + (i < 4 ? 0 : half);
             uint8_t* mp = a.masks + ((int64_t)f * a.height + y) * a.width + x0 + xoff(i);
-            const uint8_t m0 = (uint8_t)(pack_bits(e[2 * i]) << a.mask_shift);
-            const uint8_t m1 = (uint8_t)(pack_bits(e[2 * i + 1]) << a.mask_shift);
+            const uint8_t m0 = (uint8_t)(stripe_px::pack_bits(e[2 * i]) << a.mask_shift);
+            const uint8_t m1 = (uint8_t)(stripe_px::pack_bits(e[2 * i + 1]) << a.mask_shift);
             if (!__builtin_amdgcn_inverse_ballot_w64(q0)) mp[0] = a.mask_shift ? (uint8_t)(mp[0] | m0) : m0;
             if (!__builtin_amdgcn_inverse_ballot_w64(q1)) mp[1] = a.mask_shift ? (uint8_t)(mp[1] | m1) : m1;
           }

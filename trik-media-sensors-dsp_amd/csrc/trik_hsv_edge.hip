@@ -33,20 +33,13 @@
 #include <hip/hip_runtime.h>
 
 #include "trik_hsv_internal.h"
+#include "trik_hsv_wave.h"
 
 namespace trik_hsv {
 
 namespace {
 
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kEdgeBlock = 256;
-
-__device__ __forceinline__ uint32_t edge_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Byte i of the thresholded map of one frame (`in`: its Y plane, w * h bytes;
 // last = w * (h - 2) - 3, the last window of the Sobel loop).
@@ -262,8 +255,8 @@ __global__ __launch_bounds__(kEdgeBlock) void edge_map_kernel(EdgeArgs a) {
       sx += (uint32_t)c;
     }
   }
-  n = edge_wave_sum(n);
-  sx = edge_wave_sum(sx);
+  n = wave_sum(n);
+  sx = wave_sum(sx);
   if ((threadIdx.x & 63) == 0) {
     red[0][threadIdx.x >> 6] = n;
     red[1][threadIdx.x >> 6] = sx;

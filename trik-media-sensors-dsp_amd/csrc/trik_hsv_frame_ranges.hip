@@ -10,7 +10,7 @@
 //                        the group's packed ranges go to scalar registers, the
 //                        band is walked in units of 8 pixels of one row, H, S
 //                        and V of every pixel are computed once (stripe_px::
-//                        phase1, WSEQ:181-249) and tested against the 4 ranges
+//                        word_hsv, WSEQ:181-249) and tested against the 4 ranges
 //                        (detect_packed, WSEQ:171-179).  A unit's N and sum of
 //                        columns stay in 32 bits (8 pixels of one row; sum_y =
 //                        row * N) and are widened to 64 bits before units are
@@ -26,6 +26,7 @@
 #include "trik_hsv_internal.h"
 #include "trik_hsv_pixel.h"
 #include "trik_hsv_stripe_px.h"
+#include "trik_hsv_wave.h"
 
 namespace trik_hsv {
 
@@ -95,25 +96,6 @@ __device__ __forceinline__ void load_unit(const uint8_t* fr, int height, int lin
   }
 }
 
-// H, S, V of pixel PIX of a YUYV word (WSEQ:181-249): phase1's presums, 16-bit
-// wrap, clamp and hue case (G > B > R), then the two LUT products.
-template <int PIX>
-__device__ __forceinline__ void word_hsv(uint32_t w, uint32_t wc, const uint16_t* l43, const uint16_t* l255,
-                                         uint32_t& H, uint32_t& S, uint32_t& V) {
-  const stripe_px::Phase1 p = stripe_px::phase1<PIX>(w, wc, 0u);
-  const int mx = max(p.r, max(p.g, p.b)), mn = min(p.r, min(p.g, p.b));
-  const uint32_t h = p.base + (uint32_t)l43[mx - mn] * p.diff;  // mod 2^32, as the int product
-  H = (h >> 8) & 0xFFu;
-  S = ((uint32_t)l255[mx] * (uint32_t)(mx - mn)) >> 8;
-  V = (uint32_t)mx;
-}
-
-__device__ __forceinline__ uint64_t fr_wave_sum(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // One pass over the band for NR ranges from range g0 on (ranges past the
 // frame's last never match): the lanes' 64-bit sums of N, sum_x and sum_y per
 // range, reduced over the wave into red[wave].
@@ -147,8 +129,8 @@ __device__ __forceinline__ void band_pass(const FrameRangesArgs& a, const uint8_
     for (int j = 0; j < 4; ++j) {
       const uint32_t wc = w[j] ^ 0xFF00FF00u;
       uint32_t H[2], S[2], V[2];
-      word_hsv<0>(w[j], wc, l43, l255, H[0], S[0], V[0]);
-      word_hsv<1>(w[j], wc, l43, l255, H[1], S[1], V[1]);
+      stripe_px::word_hsv<0>(w[j], wc, l43, l255, H[0], S[0], V[0]);
+      stripe_px::word_hsv<1>(w[j], wc, l43, l255, H[1], S[1], V[1]);
 #pragma unroll
       for (int px = 0; px < 2; ++px)
 #pragma unroll
@@ -168,7 +150,7 @@ __device__ __forceinline__ void band_pass(const FrameRangesArgs& a, const uint8_
   }
 #pragma unroll
   for (int k = 0; k < 3 * NR; ++k) {
-    const uint64_t v = fr_wave_sum(acc[k]);
+    const uint64_t v = wave_sum(acc[k]);
     if (lane == 0) red_wave[k] = v;
   }
 }
@@ -183,6 +165,8 @@ __global__ __launch_bounds__(kFrBlock) void frame_ranges_kernel(FrameRangesArgs 
   const int T = a.n_ranges;
 
   // s_mult43_div, s_mult255_div (WSEQ:400-406), and this frame's ranges packed once
+  // (by a division per lane, not stage_luts: with the staged image the T = 1
+  // pass measured 1 % slower, its loop's code unchanged but for registers)
   l43[tid] = tid ? (uint16_t)((43u * 256u) / (uint32_t)tid) : (uint16_t)0;
   l255[tid] = tid ? (uint16_t)((255u * 256u) / (uint32_t)tid) : (uint16_t)0;
   if (tid < T) {

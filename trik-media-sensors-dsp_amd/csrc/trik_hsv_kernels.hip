@@ -17,6 +17,7 @@
 
 #include "trik_hsv_internal.h"
 #include "trik_hsv_pixel.h"
+#include "trik_hsv_wave.h"
 
 namespace trik_hsv {
 
@@ -42,12 +43,6 @@ struct Acc {
   }
 };
 
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // Block-wide reduction of the per-lane accumulators into sums[frame] (one
 // 64-bit atomic per value per workgroup and frame).
 template <int NR>
@@ -57,9 +52,9 @@ __device__ void flush(Acc<NR>& acc, int frame, const KernelArgs& a, uint64_t* sc
   uint64_t v[kVals];
 #pragma unroll
   for (int k = 0; k < NR; ++k) {
-    v[3 * k + 0] = wave_sum(acc.n[k]);
-    v[3 * k + 1] = wave_sum(acc.sx[k]);
-    v[3 * k + 2] = wave_sum(acc.sy[k]);
+    v[3 * k + 0] = wave_sum<uint64_t>(acc.n[k]);  // 64 lanes' 32-bit sums may not fit 32 bits
+    v[3 * k + 1] = wave_sum<uint64_t>(acc.sx[k]);
+    v[3 * k + 2] = wave_sum<uint64_t>(acc.sy[k]);
   }
   if (lane == 0) {
 #pragma unroll

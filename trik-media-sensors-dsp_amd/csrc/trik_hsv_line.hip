@@ -20,6 +20,7 @@
 
 #include "trik_hsv_internal.h"
 #include "trik_hsv_pixel.h"
+#include "trik_hsv_wave.h"
 
 namespace trik_hsv {
 
@@ -27,12 +28,6 @@ namespace {
 
 constexpr int kLineBlock = 256;
 constexpr int kLineRows = 8;  // rows per workgroup
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---------------------------------------------------------------------------
 // line_vec_kernel.  V = clamp8(max(R', G', B') >> 6) with R' = 74Y + 102V -
@@ -45,10 +40,9 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 // i.e. (u16)(m - mlo) <= (u16)(mhi - mlo) -- a saturating subtract is 0 iff
 // detected.  A lane holds 8 pixels as four u16x2 groups whose halves are
 // pixels 2 apart (so each half has its own chroma pair, no broadcast):
-// group g = 2h + k holds pixels 4h + k and 4h + k + 2 of the unit.
+// group g = 2h + k holds pixels 4h + k and 4h + k + 2 of the unit (u16x2 /
+// i16x2: trik_hsv_wave.h; the matrix: yuv::, trik_hsv_pixel.h).
 // ---------------------------------------------------------------------------
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
 struct LineGeom {
   int32_t units;      // 8-pixel column units per row (W / 8)
@@ -67,17 +61,17 @@ __device__ __forceinline__ void line_px8(uint32_t yw, uint32_t cw, int h, u16x2 
   // chroma bytes V0 U0 V1 U1 (ov7670: V even, U odd; OSEQ:369-373)
   const u16x2 V = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(0u, cw, 0x0c020c00u));
   const u16x2 U = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(0u, cw, 0x0c030c01u));
-  const u16x2 cR = V * (unsigned short)102 + (unsigned short)(65536 - 14248);
-  const u16x2 cG = (unsigned short)8696 - V * (unsigned short)52 - U * (unsigned short)25;
-  const u16x2 cB = U * (unsigned short)129 + (unsigned short)(65536 - 17672);
+  const u16x2 cR = V * (unsigned short)yuv::kRV + (unsigned short)yuv::kR0;  // mod 2^16
+  const u16x2 cG = (unsigned short)yuv::kG0 - V * (unsigned short)yuv::kGV - U * (unsigned short)yuv::kGU;
+  const u16x2 cB = U * (unsigned short)yuv::kBU + (unsigned short)yuv::kB0;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const u16x2 Y =
         __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(0u, yw, k ? 0x0c030c01u : 0x0c020c00u));
-    const u16x2 y74 = Y * (unsigned short)74;
-    const s16x2 r = __builtin_bit_cast(s16x2, (u16x2)(y74 + cR));
-    const s16x2 gg = __builtin_bit_cast(s16x2, (u16x2)(y74 + cG));
-    const s16x2 b = __builtin_bit_cast(s16x2, (u16x2)(y74 + cB));
+    const u16x2 y74 = Y * (unsigned short)yuv::kY;
+    const i16x2 r = __builtin_bit_cast(i16x2, (u16x2)(y74 + cR));
+    const i16x2 gg = __builtin_bit_cast(i16x2, (u16x2)(y74 + cG));
+    const i16x2 b = __builtin_bit_cast(i16x2, (u16x2)(y74 + cB));
     const u16x2 m = __builtin_bit_cast(u16x2, __builtin_elementwise_max(__builtin_elementwise_max(r, gg), b));
     // nd = min(sat(d - kspan), 1): 0 iff detected, else 1.  In asm: LLVM
     // rewrites this pair into per-half compares + selects (4+ ops instead of 2).
@@ -122,12 +116,6 @@ __device__ __forceinline__ int line_rows(const uint8_t* yp, int64_t cofs, int64_
     line_px8(y.y, c.y, 1, mlo, kspan, acc);
   }
   return k1 > k0 ? k1 - k0 : 0;
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(1024) void line_vec_kernel(LineArgs a, LineGeom g) {
@@ -176,9 +164,9 @@ __global__ __launch_bounds__(1024) void line_vec_kernel(LineArgs a, LineGeom g) 
         }
       }
   }
-  n = wave_sum_u64(n);
-  sx = wave_sum_u64(sx);
-  cross = wave_sum_u64(cross);
+  n = wave_sum(n);
+  sx = wave_sum(sx);
+  cross = wave_sum(cross);
   if ((tid & 63) == 0) {
     TrikHsvTargetSums* d = a.sums + f;
     if (n) atomicAdd(reinterpret_cast<unsigned long long*>(&d->points), (unsigned long long)n);
@@ -215,9 +203,9 @@ __global__ __launch_bounds__(kLineBlock) void line_sums_kernel(LineArgs a) {
     sx += row_x;
     if ((uint32_t)row >= (uint32_t)a.band_start && (uint32_t)row <= (uint32_t)a.band_stop) cross += row_n;
   }
-  n = wave_sum_u32(n);
-  sx = wave_sum_u32(sx);
-  cross = wave_sum_u32(cross);
+  n = wave_sum(n);
+  sx = wave_sum(sx);
+  cross = wave_sum(cross);
   if ((threadIdx.x & 63) == 0) {
     TrikHsvTargetSums* d = a.sums + f;
     if (n) atomicAdd(reinterpret_cast<unsigned long long*>(&d->points), (unsigned long long)n);

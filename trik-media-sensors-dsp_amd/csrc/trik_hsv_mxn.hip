@@ -45,22 +45,12 @@ struct MxnGeom {
 };
 
 // The histogram bin (H >> 3) << 4 | (S >> 6) << 2 | V >> 6 of one pixel given
-// as a word with Y in byte 0, U in byte 1 and V in byte 3: the branch-free
-// form of MSEQ:191-249 the hot kernel and the auto-range histogram use
-// (trik_hsv_stripe_px.h: 16-bit sums through v_dot4, the hue case as selects).
+// as a word with Y in byte 0, U in byte 1 and V in byte 3: MSEQ:191-249 in the
+// word form (stripe_px::word_hsv, trik_hsv_stripe_px.h).
 __device__ __forceinline__ uint32_t mxn_bin(uint32_t w, const uint16_t* l43, const uint16_t* l255) {
-  using stripe_px::clamp8_shift6;
-  const uint32_t wc = w ^ 0xFF00FF00u;
-  const int r = clamp8_shift6(__builtin_amdgcn_udot4(w, 74u | (102u << 24), (uint32_t)-14248, false));
-  const int g = clamp8_shift6(__builtin_amdgcn_udot4(wc, 74u | (25u << 8) | (52u << 24), (uint32_t)-10939, false));
-  const int b = clamp8_shift6(__builtin_amdgcn_udot4(w, 74u | (129u << 8), (uint32_t)-17672, false));
-  const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
-  const bool eqG = mx == g, eqB = mx == b;  // priority G > B > R (MSEQ:226-246)
-  const int diff = eqG ? b - r : (eqB ? r - g : g - b);
-  const int base = eqG ? 21845 : (eqB ? 43690 : 0);
-  const uint32_t h = (uint32_t)(base + (int)l43[mx - mn] * diff);
-  const uint32_t sat = ((uint32_t)l255[mx] * (uint32_t)(mx - mn)) >> 8;
-  return ((h >> 7) & 0x1F0u) | ((sat >> 6) << 2) | ((uint32_t)mx >> 6);
+  uint32_t H, S, V;
+  stripe_px::word_hsv<0>(w, w ^ 0xFF00FF00u, l43, l255, H, S, V);
+  return ((H >> 3) << 4) | ((S >> 6) << 2) | (V >> 6);
 }
 
 // One pixel slot of a wave: lanes with `in` set add their bin (pos1 = raster
@@ -106,10 +96,7 @@ __global__ __launch_bounds__(kMxnBlock) void mxn_hist_kernel(MxnArgs a, MxnGeom 
     (&cnt[0][0])[i] = 0u;
     (&lst[0][0])[i] = 0u;
   }
-  if (tid < 256) {  // s_mult43_div, s_mult255_div (MSEQ:564-570)
-    l43[tid] = tid ? (uint16_t)((43u * 256u) / (uint32_t)tid) : (uint16_t)0;
-    l255[tid] = tid ? (uint16_t)((255u * 256u) / (uint32_t)tid) : (uint16_t)0;
-  }
+  stage_luts(l43, l255, tid, kMxnBlock);  // s_mult43_div, s_mult255_div (MSEQ:564-570)
   __syncthreads();
 
   // The cell's rows walked in aligned 4-pixel groups (frame columns 4g..4g+3,

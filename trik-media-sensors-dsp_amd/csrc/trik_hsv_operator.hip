@@ -26,13 +26,11 @@
 #include "trik_hsv_internal.h"
 #include "trik_hsv_pixel.h"
 #include "trik_hsv_stripe_px.h"
+#include "trik_hsv_wave.h"
 
 namespace trik_hsv {
 
 namespace {
-
-__constant__ Luts c_luts = make_luts();  // trik_hsv_pixel.h
-
 
 // The preview as a grid-stride gather over 4-byte output groups (two output
 // pixels each) of the whole batch: 1024-lane workgroups, two per CU, the
@@ -389,12 +387,10 @@ __global__ __launch_bounds__(64) void overlay_kernel(PreviewArgs a, const TrikHs
 constexpr int kRangeBlock = 256;
 constexpr int kRangeWideFrames = 32;  // batches up to this size: 1024 lanes per frame
 
-// H, S, V bytes of one pixel (WSEQ:207-249), branch-free as the hot kernel's
-// phase1 (clamp8_shift6 on v_dot4 presums, the hue case as selects), with
-// LUT43 / LUT255 in LDS.
+// H, S, V bytes of one pixel (WSEQ:207-249): the pixel fetched as a YUYV word,
+// then the word form (stripe_px::word_hsv) with LUT43 / LUT255 in LDS.
 __device__ __forceinline__ void hsv_bytes(const uint8_t* fr, const AutoRangeArgs& a, int row, int col,
                                           const uint16_t* l43, const uint16_t* l255, uint32_t (&hsv)[3]) {
-  using stripe_px::clamp8_shift6;
   uint32_t w;  // the pixel as a YUYV word with its Y in byte 0
   if (a.layout == TRIK_HSV_LAYOUT_YUYV && a.aligned4) {
     w = *reinterpret_cast<const uint32_t*>(fr + (int64_t)row * a.line_length + 4 * (col >> 1));
@@ -404,18 +400,7 @@ __device__ __forceinline__ void hsv_bytes(const uint8_t* fr, const AutoRangeArgs
     fetch_yuv(fr, a.height, a.line_length, a.layout, row, col, Y, U, V);
     w = (uint32_t)Y | ((uint32_t)U << 8) | ((uint32_t)V << 24);
   }
-  const uint32_t wc = w ^ 0xFF00FF00u;
-  const int r = clamp8_shift6(__builtin_amdgcn_udot4(w, 74u | (102u << 24), (uint32_t)-14248, false));
-  const int g = clamp8_shift6(__builtin_amdgcn_udot4(wc, 74u | (25u << 8) | (52u << 24), (uint32_t)-10939, false));
-  const int b = clamp8_shift6(__builtin_amdgcn_udot4(w, 74u | (129u << 8), (uint32_t)-17672, false));
-  const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
-  const bool eqG = mx == g, eqB = mx == b;  // priority G > B > R (WSEQ:226-246)
-  const int diff = eqG ? b - r : (eqB ? r - g : g - b);
-  const int base = eqG ? 21845 : (eqB ? 43690 : 0);
-  const int h = base + (int)l43[mx - mn] * diff;
-  hsv[0] = ((uint32_t)h >> 8) & 0xFFu;
-  hsv[1] = ((uint32_t)l255[mx] * (uint32_t)(mx - mn)) >> 8;
-  hsv[2] = (uint32_t)mx;
+  stripe_px::word_hsv<0>(w, w ^ 0xFF00FF00u, l43, l255, hsv[0], hsv[1], hsv[2]);
 }
 
 // One H (or S, V) value per lane into the histograms, for a wave whose active
@@ -461,10 +446,7 @@ __global__ __launch_bounds__(kBlock) void auto_range_kernel(AutoRangeArgs a) {
   const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
   for (int i = tid; i < kWaves * 3 * 256; i += blockDim.x) (&cnt[0][0][0])[i] = 0;
   for (int i = tid; i < kLastSets * 3 * 256; i += blockDim.x) (&lst[0][0][0])[i] = 0;
-  for (int i = tid; i < 256; i += blockDim.x) {
-    l43[i] = c_luts.l43[i];
-    l255[i] = c_luts.l255[i];
-  }
+  stage_luts(l43, l255, tid, blockDim.x);
   if (tid < 3) {
     best_n[tid] = 0;
     best[tid] = ~0ull;
@@ -553,12 +535,9 @@ struct AutoVecGeom {
   int32_t lo_f, hi_l;  // a row's first chunk: pixels p < lo_f lie left of the zone; its last: p >= hi_l right of it
 };
 
-// Two pixels in the 16-bit halves of one register (packed VOP3P arithmetic;
-// plain vector types and builtins, so the compiler schedules the packed ops
-// and inserts their wait states -- an inline-asm form computed wrong S values
-// under another schedule, scripts/ab/r06u_hsv3.py)
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
+// Two pixels in the 16-bit halves of one register (u16x2 / i16x2,
+// trik_hsv_wave.h: plain vector types and builtins -- an inline-asm form
+// computed wrong S values under another schedule, scripts/ab/r06u_hsv3.py)
 
 // One of R, G, B for both pixels of a word: Y holds Y0 and Y1 in its halves,
 // c the channel's chroma term (its low 16 bits, used for both).  (74 Y + c)
@@ -567,7 +546,7 @@ typedef short i16x2 __attribute__((ext_vector_type(2)));
 // (WSEQ:181-205; clamp8_shift6 per pixel).
 __device__ __forceinline__ i16x2 pk_chan(u16x2 Y, uint32_t c) {
   const u16x2 cc = {(unsigned short)c, (unsigned short)c};
-  const u16x2 x = Y * (u16x2){74, 74} + cc;
+  const u16x2 x = Y * (u16x2){yuv::kY, yuv::kY} + cc;
   const i16x2 s = __builtin_bit_cast(i16x2, x) >> (i16x2){6, 6};
   return __builtin_elementwise_min(__builtin_elementwise_max(s, (i16x2){0, 0}), (i16x2){255, 255});
 }
@@ -579,11 +558,12 @@ __device__ __forceinline__ i16x2 pk_chan(u16x2 Y, uint32_t c) {
 // against 66 and two divergent branches per pixel for hsv_bytes' form.
 __device__ __forceinline__ void hsv_pair(uint32_t w, const uint16_t* l43, const uint16_t* l255, uint32_t (&p0)[3],
                                          uint32_t (&p1)[3]) {
-  const uint32_t wc = w ^ 0xFF00FF00u;
   // the chroma terms (Y weight 0); their low 16 bits are the wrapped sums' offsets
-  const uint32_t cr = __builtin_amdgcn_udot4(w, 102u << 24, (uint32_t)-14248, false);
-  const uint32_t cg = __builtin_amdgcn_udot4(wc, (25u << 8) | (52u << 24), (uint32_t)-10939, false);
-  const uint32_t cb = __builtin_amdgcn_udot4(w, 129u << 8, (uint32_t)-17672, false);
+  using namespace stripe_px;
+  const uint32_t wc = w ^ 0xFF00FF00u;
+  const uint32_t cr = presum<kChromaTerms, kR>(w, wc);
+  const uint32_t cg = presum<kChromaTerms, kG>(w, wc);
+  const uint32_t cb = presum<kChromaTerms, kB>(w, wc);
   const u16x2 Y = __builtin_bit_cast(u16x2, w & 0x00FF00FFu);
   const i16x2 R = pk_chan(Y, cr), G = pk_chan(Y, cg), B = pk_chan(Y, cb);
   const i16x2 MX = __builtin_elementwise_max(__builtin_elementwise_max(R, G), B);
@@ -592,7 +572,7 @@ __device__ __forceinline__ void hsv_pair(uint32_t w, const uint16_t* l43, const 
   // priority G > B > R (WSEQ:226-246)
   const bool eg0 = MX.x == G.x, eb0 = MX.x == B.x, eg1 = MX.y == G.y, eb1 = MX.y == B.y;
   const i16x2 df0 = eg0 ? dBR : (eb0 ? dRG : dGB), df1 = eg1 ? dBR : (eb1 ? dRG : dGB);
-  const int b0 = eg0 ? 21845 : (eb0 ? 43690 : 0), b1 = eg1 ? 21845 : (eb1 ? 43690 : 0);
+  const int b0 = eg0 ? kHueBaseG : (eb0 ? kHueBaseB : 0), b1 = eg1 ? kHueBaseG : (eb1 ? kHueBaseB : 0);
   const uint32_t d0 = (uint16_t)D.x, d1 = (uint16_t)D.y, m0 = (uint16_t)MX.x, m1 = (uint16_t)MX.y;
   const int h0 = b0 + (int)l43[d0] * (int)df0.x, h1 = b1 + (int)l43[d1] * (int)df1.y;
   p0[0] = ((uint32_t)h0 >> 8) & 0xFFu;
@@ -617,10 +597,7 @@ __global__ __launch_bounds__(kRangeBlock) void auto_range_vec_kernel(AutoRangeAr
   const int f = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
   for (int i = tid; i < kWaves * 3 * 256; i += kRangeBlock) (&cnt[0][0][0])[i] = 0;
   for (int i = tid; i < 3 * 256; i += kRangeBlock) (&lst[0][0])[i] = 0;
-  for (int i = tid; i < 256; i += kRangeBlock) {
-    l43[i] = c_luts.l43[i];
-    l255[i] = c_luts.l255[i];
-  }
+  stage_luts(l43, l255, tid, kRangeBlock);
   if (tid < 3) {
     top_n[tid] = 0;
     n_top[tid] = 0;

@@ -1,8 +1,9 @@
-// trik_hsv_pixel.h -- per-pixel arithmetic of the reference path, as plain
-// device functions, for the kernels that visit pixels individually (the
-// generic reduce kernel, the preview and the HSV histogram).  The hot stripe
-// kernel has its own instruction-tuned form of the same arithmetic
-// (trik_hsv_stripe.hip); the exhaustive parity tests hold both to the oracle.
+// trik_hsv_pixel.h -- per-pixel arithmetic of the reference path in its scalar
+// form, for the kernels that visit pixels individually (the generic reduce
+// kernel, the preview and the histograms): the YUV -> RGB matrix as named
+// constants, pixel_rgb, and one body for H, S and V, pixel_hsv_bytes.  The
+// word form (trik_hsv_stripe_px.h) is built on the same constants; the
+// exhaustive parity tests hold both to the oracle.
 //
 // SURVEY Appendix A; equal to WSEQ:181-249 (WSEQ as in include/trik_hsv.h) on
 // all 2^24 (Y, U, V) inputs.
@@ -11,6 +12,16 @@
 #include "trik_hsv_internal.h"
 
 namespace trik_hsv {
+
+// convert2xYuyvToRgb888's fixed-point matrix (WSEQ:181-201), the one copy:
+// R' = 74 Y + 102 V - 14248, G' = 74 Y - 25 U - 52 V + 8696,
+// B' = 74 Y + 129 U - 17672 (16-bit sums: B' wraps), channel = clamp8(x' >> 6).
+namespace yuv {
+constexpr int kY = 74, kRV = 102, kGU = 25, kGV = 52, kBU = 129;
+constexpr int kR0 = -14248, kG0 = 8696, kB0 = -17672;
+}  // namespace yuv
+// convertRgb888ToHsv's hue offsets of the G and B cases (WSEQ:226-246): 1/3 and 2/3 of 2^16
+constexpr int kHueBaseG = 21845, kHueBaseB = 43690;
 
 __device__ __forceinline__ int clamp8(int v) { return min(max(v, 0), 255); }
 
@@ -23,41 +34,37 @@ struct PixelRgb {
 
 // convert2xYuyvToRgb888, WSEQ:181-205
 __device__ __forceinline__ PixelRgb pixel_rgb(int Y, int U, int V) {
-  const int y74 = 74 * Y;
+  const int y74 = yuv::kY * Y;
   PixelRgb p;
-  p.r = clamp8((102 * V + y74 - 14248) >> 6);
-  p.g = clamp8((-52 * V - 25 * U + y74 + 8696) >> 6);
-  p.b = clamp8(((int)(int16_t)(129 * U + y74 - 17672)) >> 6);  // _add2 wraps at 16 bits
+  p.r = clamp8((yuv::kRV * V + y74 + yuv::kR0) >> 6);
+  p.g = clamp8((-yuv::kGV * V - yuv::kGU * U + y74 + yuv::kG0) >> 6);
+  p.b = clamp8(((int)(int16_t)(yuv::kBU * U + y74 + yuv::kB0)) >> 6);  // _add2 wraps at 16 bits
   return p;
 }
 
-// convertRgb888ToHsv hue byte, WSEQ:207-249 (G > B > R on ties)
-__device__ __forceinline__ uint32_t pixel_hue(const PixelRgb& p, int mx, int mn, const RangeTables& t) {
-  const int m = t.lut43[mx - mn];
+// H, S, V bytes (WSEQ:207-249; hue priority G > B > R on ties), the scalar
+// form's one body, with LUT43 / LUT255 from any address space.
+template <typename L>
+__device__ __forceinline__ void pixel_hsv_bytes(const PixelRgb& p, const L* l43, const L* l255, uint32_t& H,
+                                                uint32_t& S, uint32_t& V) {
+  const int mx = max(p.r, max(p.g, p.b)), mn = min(p.r, min(p.g, p.b));
+  const int m = l43[mx - mn];
   int h;
-  if (mx == p.g)
-    h = 21845 + m * (p.b - p.r);
-  else if (mx == p.b)
-    h = 43690 + m * (p.r - p.g);
-  else
-    h = m * (p.g - p.b);
-  return ((uint32_t)h >> 8) & 0xFFu;
+  if (mx == p.g) h = kHueBaseG + m * (p.b - p.r);
+  else if (mx == p.b) h = kHueBaseB + m * (p.r - p.g);
+  else h = m * (p.g - p.b);
+  H = ((uint32_t)h >> 8) & 0xFFu;
+  S = ((uint32_t)l255[mx] * (uint32_t)(mx - mn)) >> 8;
+  V = (uint32_t)mx;
 }
 
 // (Y,U,V) -> T-bit mask of the ranges whose H, S and V tests all pass.
 __device__ __forceinline__ uint32_t detect_pixel(int Y, int U, int V, const RangeTables& t) {
   const PixelRgb p = pixel_rgb(Y, U, V);
-  const int mx = max(p.r, max(p.g, p.b));
-  const int mn = min(p.r, min(p.g, p.b));
-  return (uint32_t)t.hue[pixel_hue(p, mx, mn, t)] & (uint32_t)t.sv[(mx << 8) | mn];
-}
-
-// Full HSV word V<<16 | S<<8 | H (WSEQ:207-249), S = (LUT255[max]*delta)>>8.
-__device__ __forceinline__ uint32_t pixel_hsv(const PixelRgb& p, const RangeTables& t) {
-  const int mx = max(p.r, max(p.g, p.b));
-  const int mn = min(p.r, min(p.g, p.b));
-  const uint32_t s = ((uint32_t)t.lut255[mx] * (uint32_t)(mx - mn)) >> 8;
-  return ((uint32_t)mx << 16) | (s << 8) | pixel_hue(p, mx, mn, t);
+  uint32_t H, S, mx;
+  pixel_hsv_bytes(p, t.lut43, t.lut255, H, S, mx);
+  const uint32_t mn = (uint32_t)min(p.r, min(p.g, p.b));
+  return (uint32_t)t.hue[H] & (uint32_t)t.sv[(mx << 8) | mn];
 }
 
 // detectHsvPixel (WSEQ:171-179) for one packed range: per-byte "outside the
@@ -69,8 +76,8 @@ __device__ __forceinline__ bool detect_packed(uint32_t H, uint32_t S, uint32_t V
   return out == r.expect;
 }
 
-// s_mult43_div and s_mult255_div (WSEQ:400-406) as a compile-time image: a
-// kernel file that needs them outside RangeTables keeps one __constant__ copy.
+// s_mult43_div and s_mult255_div (WSEQ:400-406) as a compile-time image, staged
+// into a kernel's LDS by its workgroup's n lanes (the caller's barrier follows)
 struct Luts {
   uint16_t l43[256], l255[256];
 };
@@ -82,20 +89,14 @@ constexpr Luts make_luts() {
   }
   return l;
 }
-
-// H, S, V bytes (WSEQ:207-249) with LUT43 / LUT255 from any address space.
-template <typename L>
-__device__ __forceinline__ void pixel_hsv_bytes(const PixelRgb& p, const L* l43, const L* l255, uint32_t& H,
-                                                uint32_t& S, uint32_t& V) {
-  const int mx = max(p.r, max(p.g, p.b)), mn = min(p.r, min(p.g, p.b));
-  const int m = l43[mx - mn];
-  int h;
-  if (mx == p.g) h = 21845 + m * (p.b - p.r);
-  else if (mx == p.b) h = 43690 + m * (p.r - p.g);
-  else h = m * (p.g - p.b);
-  H = ((uint32_t)h >> 8) & 0xFFu;
-  S = ((uint32_t)l255[mx] * (uint32_t)(mx - mn)) >> 8;
-  V = (uint32_t)mx;
+namespace {
+__constant__ Luts c_luts = make_luts();  // one copy per kernel file that stages them
+}
+__device__ __forceinline__ void stage_luts(uint16_t* l43, uint16_t* l255, int tid, int n) {
+  for (int i = tid; i < 256; i += n) {
+    l43[i] = c_luts.l43[i];
+    l255[i] = c_luts.l255[i];
+  }
 }
 
 // writeOutputPixel, WSEQ:66-70: 0x00RRGGBB -> B5 G6 R5 (R in the low bits),

@@ -116,11 +116,6 @@ __device__ __forceinline__ void load_chunk(const uint8_t* p, int64_t plane, uint
   }
 }
 
-// byte-spread mask -> bit mask (range t -> bit t)
-__device__ __forceinline__ uint32_t pack_bits(uint32_t e) {
-  return ((e * 0x01020408u) >> 24) & 0xFu;  // bit 8t lands on bit 24+t
-}
-
 // MODE (KernelArgs::detect_mode): the detection a launch group needs.
 //  kDetectFull  the full pixel path above.
 //  kDetectSV    every range accepts every hue (the S- and V-band sets): the

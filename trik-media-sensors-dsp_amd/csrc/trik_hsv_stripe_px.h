@@ -1,12 +1,16 @@
-// trik_hsv_stripe_px.h -- the hot kernel's per-pixel arithmetic (YUYV word ->
-// detection mask via the StripeTables LDS image), shared by stripe_kernel
-// (trik_hsv_stripe.hip) and the multi-blob bitmap kernel (trik_hsv_blob.hip).
-// Both stage the StripeTables image at LDS address 0 (no static LDS).
+// trik_hsv_stripe_px.h -- the per-pixel arithmetic in its word form (pixel PIX
+// of a YUYV word, branch-free on v_dot4 presums), each step written once:
+// presum, clamp8_shift6 / rgb, hue_case, and word_hsv for kernels that need H,
+// S, V.  On top of them the hot kernels' table addressing over the
+// StripeTables image at LDS address 0 (phase1, sv_addr_only, v_addr,
+// phase2_addr, combine).  The scalar form, the matrix constants and the LUT
+// staging helper are trik_hsv_pixel.h's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "trik_hsv_internal.h"
+#include "trik_hsv_pixel.h"
 
 namespace trik_hsv {
 namespace stripe_px {
@@ -20,18 +24,56 @@ typedef __attribute__((address_space(3))) const uint32_t* lds_u32_ptr;
 __device__ __forceinline__ uint32_t lds_u32(uint32_t addr) { return *(lds_u32_ptr)(uintptr_t)addr; }
 __device__ __forceinline__ uint32_t lds_u8(uint32_t addr) { return *(lds_u8_ptr)(uintptr_t)addr; }
 
-// Phase 1 for both pixels of a YUYV word w (b0=Y0, b1=U, b2=Y1, b3=V):
-//  * presums of WSEQ:183-201 with v_dot4_u32_u8; wc =
-//    w ^ 0xFF00FF00 carries complemented chroma for the negative G weights
-//    (WSEQ:188-190);
-//  * x = (int16)presum >> 6 clamped to [0, 255] (WSEQ:203-205): the
-//    reference's _add2 keeps 16-bit lanes, so only bits 15:0 of the presum
-//    matter (B wraps for 27,136 triples) -- one v_bfe_i32 + one v_med3_i32;
-//  * max, min (WSEQ:207-216) and the hue case select of WSEQ:226-246
-//    (priority G > B > R on ties): diff and base;
-//  * LDS byte addresses of this pixel's LUT43[max - min] copy (per-bank
-//    replicated row, StripeTables::rows) and of its sat&val mask
-//    sv[max * 260 + min].
+// Presum CH of WSEQ:183-201 for pixel PIX of a YUYV word w
+// (b0=Y0, b1=U, b2=Y1, b3=V), one v_dot4_u32_u8; wc = w ^ 0xFF00FF00 carries
+// complemented chroma for the negative G weights (WSEQ:188-190).  The
+// reference's _add2 keeps 16-bit lanes, so only bits 15:0 matter (B wraps for
+// 27,136 triples).  PIX = kChromaTerms: Y weight 0 (the packed 16-bit forms
+// add 74 Y themselves).  One call per channel: a caller keeps its own order
+// of dot products and clamps, which the hot kernels' schedules follow.
+enum { kR, kG, kB };
+constexpr int kChromaTerms = -1;
+template <int PIX, int CH>
+__device__ __forceinline__ uint32_t presum(uint32_t w, uint32_t wc) {
+  constexpr uint32_t kY = PIX < 0 ? 0u : (uint32_t)yuv::kY << (16 * PIX);
+  constexpr uint32_t kG0c = (uint32_t)(yuv::kG0 - 255 * (yuv::kGU + yuv::kGV));  // -10939
+  if (CH == kR) return __builtin_amdgcn_udot4(w, kY | ((uint32_t)yuv::kRV << 24), (uint32_t)yuv::kR0, false);
+  if (CH == kG)
+    return __builtin_amdgcn_udot4(wc, kY | ((uint32_t)yuv::kGU << 8) | ((uint32_t)yuv::kGV << 24), kG0c, false);
+  return __builtin_amdgcn_udot4(w, kY | ((uint32_t)yuv::kBU << 8), (uint32_t)yuv::kB0, false);
+}
+
+// x = (int16)presum >> 6 clamped to [0, 255] (WSEQ:203-205): v_bfe_i32 + v_med3_i32
+__device__ __forceinline__ int shift6(uint32_t s) { return ((int)(s << 16)) >> 22; }  // bits 15:6, sign from 15
+__device__ __forceinline__ int clamp8_shift6(uint32_t s) {
+  const int x = shift6(s);
+  const int lo = x < 0 ? 0 : x;
+  return lo > 255 ? 255 : lo;  // v_med3_i32
+}
+template <int PIX>
+__device__ __forceinline__ PixelRgb rgb(uint32_t w, uint32_t wc) {
+  PixelRgb p;
+  p.r = clamp8_shift6(presum<PIX, kR>(w, wc));
+  p.g = clamp8_shift6(presum<PIX, kG>(w, wc));
+  p.b = clamp8_shift6(presum<PIX, kB>(w, wc));
+  return p;
+}
+
+// The hue case select of WSEQ:226-246 (priority G > B > R on ties) as
+// selects: h = base + LUT43[max - min] * diff.
+__device__ __forceinline__ void hue_case(const PixelRgb& p, int mx, uint32_t& diff, uint32_t& base) {
+  const bool eqG = mx == p.g, eqB = mx == p.b;
+  const int dR = p.g - p.b, dG = p.b - p.r, dB = p.r - p.g;
+  const int d = eqB ? dB : dR;
+  diff = (uint32_t)(eqG ? dG : d);
+  const uint32_t b = eqB ? (uint32_t)kHueBaseB : 0u;
+  base = eqG ? (uint32_t)kHueBaseG : b;
+}
+
+// Phase 1 of the hot kernel for pixel PIX of a word: rgb, max, min
+// (WSEQ:207-216), the hue case, and the LDS byte addresses of this pixel's
+// LUT43[max - min] copy (per-bank replicated row, StripeTables::rows) and of
+// its sat&val mask sv[max * 260 + min].
 // Plain 32-bit code: on gfx950 this kernel's time follows its VALU
 // instruction count (the 16-bit full-rate forms measured no faster in
 // context, scripts/ubench/pixel_mix.hip), and the compiler schedules it and
@@ -45,33 +87,34 @@ constexpr int log2i(int v) { return v <= 1 ? 0 : 1 + log2i(v / 2); }
 constexpr int kM43Shift = log2i(4 * kM43Copies);  // byte stride of one m43 entry's copies
 constexpr int kHueShift = log2i(4 * kHueCopies);
 static_assert((1 << kM43Shift) == 4 * kM43Copies && (1 << kHueShift) == 4 * kHueCopies, "pow2 copies");
-__device__ __forceinline__ int clamp8_shift6(uint32_t s) {
-  const int x = ((int)(s << 16)) >> 22;  // bits 15:6, sign from 15 (v_bfe_i32)
-  const int lo = x < 0 ? 0 : x;
-  return lo > 255 ? 255 : lo;            // v_med3_i32
-}
 template <int PIX>
 __device__ __forceinline__ Phase1 phase1(uint32_t w, uint32_t wc, uint32_t m43_lane) {
-  constexpr uint32_t kY = PIX == 0 ? 74u : (74u << 16);
-  const int r = clamp8_shift6(__builtin_amdgcn_udot4(w, kY | (102u << 24), (uint32_t)-14248, false));
-  const int g = clamp8_shift6(__builtin_amdgcn_udot4(wc, kY | (25u << 8) | (52u << 24), (uint32_t)-10939, false));
-  const int b = clamp8_shift6(__builtin_amdgcn_udot4(w, kY | (129u << 8), (uint32_t)-17672, false));
-  const int mx = max(r, max(g, b));
-  const int mn = min(r, min(g, b));
+  const PixelRgb c = rgb<PIX>(w, wc);
+  const int mx = max(c.r, max(c.g, c.b));
+  const int mn = min(c.r, min(c.g, c.b));
   Phase1 p;
-  p.rgb888 = ((uint32_t)r << 16) | ((uint32_t)g << 8) | (uint32_t)b;
-  p.r = r;
-  p.g = g;
-  p.b = b;
+  p.rgb888 = c.rgb888();
+  p.r = c.r;
+  p.g = c.g;
+  p.b = c.b;
   p.m43_addr = ((uint32_t)(mx - mn) << kM43Shift) + m43_lane;
   p.sv_addr = __umul24((uint32_t)mx, (uint32_t)kSvStride) + (uint32_t)mn;
-  const bool eqG = mx == g, eqB = mx == b;
-  const int dR = g - b, dG = b - r, dB = r - g;
-  int diff = eqB ? dB : dR;
-  p.diff = (uint32_t)(eqG ? dG : diff);
-  uint32_t base = eqB ? 43690u : 0u;
-  p.base = eqG ? 21845u : base;
+  hue_case(c, mx, p.diff, p.base);
   return p;
+}
+
+// H, S, V of pixel PIX of a YUYV word (WSEQ:181-249) with LUT43 / LUT255 from
+// any address space: phase1 (its table addresses are dead code here), then
+// the two LUT products (h mod 2^32, as the int product).
+template <int PIX, typename L>
+__device__ __forceinline__ void word_hsv(uint32_t w, uint32_t wc, const L* l43, const L* l255, uint32_t& H,
+                                         uint32_t& S, uint32_t& V) {
+  const Phase1 p = phase1<PIX>(w, wc, 0u);
+  const int mx = max(p.r, max(p.g, p.b)), mn = min(p.r, min(p.g, p.b));
+  const uint32_t h = p.base + (uint32_t)l43[mx - mn] * p.diff;
+  H = (h >> 8) & 0xFFu;
+  S = ((uint32_t)l255[mx] * (uint32_t)(mx - mn)) >> 8;
+  V = (uint32_t)mx;
 }
 
 // The sat&val table address alone (ranges that accept every hue): clamp8 is
@@ -79,11 +122,9 @@ __device__ __forceinline__ Phase1 phase1(uint32_t w, uint32_t wc, uint32_t m43_l
 // of the unclamped ones (two clamps per pixel instead of three).
 template <int PIX>
 __device__ __forceinline__ uint32_t sv_addr_only(uint32_t w, uint32_t wc) {
-  constexpr uint32_t kY = PIX == 0 ? 74u : (74u << 16);
-  auto shift6 = [](uint32_t s) { return ((int)(s << 16)) >> 22; };  // v_bfe_i32 s, 6, 10
-  const int r = shift6(__builtin_amdgcn_udot4(w, kY | (102u << 24), (uint32_t)-14248, false));
-  const int g = shift6(__builtin_amdgcn_udot4(wc, kY | (25u << 8) | (52u << 24), (uint32_t)-10939, false));
-  const int b = shift6(__builtin_amdgcn_udot4(w, kY | (129u << 8), (uint32_t)-17672, false));
+  const int r = shift6(presum<PIX, kR>(w, wc));  // v_bfe_i32 s, 6, 10
+  const int g = shift6(presum<PIX, kG>(w, wc));
+  const int b = shift6(presum<PIX, kB>(w, wc));
   const int mx = min(max(max(r, max(g, b)), 0), 255);
   const int mn = min(max(min(r, min(g, b)), 0), 255);
   return __umul24((uint32_t)mx, (uint32_t)kSvStride) + (uint32_t)mn;
@@ -95,10 +136,9 @@ __device__ __forceinline__ uint32_t sv_addr_only(uint32_t w, uint32_t wc) {
 // entries below 512 / above 767 hold V = 0 / V = 255 (the clamp).
 template <int PIX>
 __device__ __forceinline__ uint32_t v_addr(uint32_t w, uint32_t wc) {
-  constexpr uint32_t kY = PIX == 0 ? 74u : (74u << 16);
-  const int r = (int)__builtin_amdgcn_udot4(w, kY | (102u << 24), (uint32_t)-14248, false);  // int16 range
-  const int g = (int)__builtin_amdgcn_udot4(wc, kY | (25u << 8) | (52u << 24), (uint32_t)-10939, false);
-  const int b = ((int)(__builtin_amdgcn_udot4(w, kY | (129u << 8), (uint32_t)-17672, false) << 16)) >> 16;
+  const int r = (int)presum<PIX, kR>(w, wc);  // int16 range
+  const int g = (int)presum<PIX, kG>(w, wc);
+  const int b = ((int)(presum<PIX, kB>(w, wc) << 16)) >> 16;
   const int m = max(r, max(g, b));
   return (uint32_t)(((m >> 6) + 512) << 2);
 }
@@ -118,6 +158,9 @@ __device__ __forceinline__ uint32_t phase2_addr(uint32_t m, const Phase1& p, uin
 __device__ __forceinline__ uint32_t combine(uint32_t hue, uint32_t sv) {
   return hue & __umul24(sv, 0x00204081u);
 }
+
+// byte-spread mask -> bit mask (range t -> bit t): bit 8t lands on bit 24+t
+__device__ __forceinline__ uint32_t pack_bits(uint32_t e) { return ((e * 0x01020408u) >> 24) & 0xFu; }
 
 // ov7670 planes -> the two YUYV words of 4 pixels (OSEQ:360-373: U = odd
 // chroma byte, V = even chroma byte): yy = Y0..Y3, cc = V0 U0 V1 U1.

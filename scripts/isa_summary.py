@@ -9,6 +9,9 @@ For every kernel symbol: instruction count, VGPRs, SGPRs, static LDS bytes and
 scratch bytes before -> after, and how the instruction stream compares:
   same   identical text
   regs   identical once register numbers are masked
+  kernarg  identical once, besides, the immediate operands of scalar loads and
+         scalar adds are masked: the kernel arguments moved (a member added to
+         or reordered in the argument struct), the code did not
   DIFF   anything else
 """
 import glob
@@ -19,6 +22,15 @@ import sys
 
 INFO = {"NumVgprs": "vgpr", "TotalNumSgprs": "sgpr", "ScratchSize": "scratch", "LDSByteSize": "lds"}
 REG = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
+IMM = re.compile(r"(?<![\w#])(0x[0-9a-f]+|-?\d+)\b")
+SCALAR = ("s_load_dword", "s_add_u32", "s_addc_u32", "s_add_i32", ".amdhsa_kernarg_size")
+
+
+def masked(ins, kernarg):
+    """The instruction without its register numbers, and, for the kernarg
+    class, without the immediates of a scalar load or add."""
+    out = REG.sub(r"\1#", ins)
+    return IMM.sub("#", out) if kernarg and out.startswith(SCALAR) else out
 
 
 def kernels(path):
@@ -71,8 +83,10 @@ def main():
                 continue
             if a["ins"] == b["ins"]:
                 stream = "same"
-            elif [REG.sub(r"\1#", i) for i in a["ins"]] == [REG.sub(r"\1#", i) for i in b["ins"]]:
+            elif [masked(i, False) for i in a["ins"]] == [masked(i, False) for i in b["ins"]]:
                 stream = "regs"
+            elif [masked(i, True) for i in a["ins"]] == [masked(i, True) for i in b["ins"]]:
+                stream = "kernarg"
             else:
                 stream = "DIFF"
             cols = ["%d->%d" % (b[k], a[k]) if b[k] != a[k] else "%d" % a[k] for k in ("vgpr", "sgpr", "lds", "scratch")]

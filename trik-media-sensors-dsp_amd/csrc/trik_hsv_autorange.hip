@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kAutoBlock) void auto_exact_kernel(AutoExactArgs a)
   __shared__ int32_t start_cell[2];    // cell, max_value
   const int f = blockIdx.x, tid = threadIdx.x;
   const int W = a.width, H = a.height;
-  const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* fr = frame_ptr(a, f);
   for (int i = tid; i < kBins; i += kAutoBlock) {
     hist[i] = 0;
     last_col[i] = -1;

@@ -62,19 +62,54 @@ int32_t check_ov7670(const TrikHsvFrameBatch* b, const char* sensor) {
   return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("the ") + sensor + " sensor takes the ov7670 layout (YUV422P)");
 }
 
-// The preview-output geometry of a preview entry point; *pb: bytes of one
-// preview.  `buffers`: every buffer the call needs is there.  The object
+// Handle and batch, then the layout, of an ov7670 sensor's entry point.
+int32_t check_ov7670_call(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, const char* sensor) {
+  const int32_t rc = check_handle_batch(h, b);
+  return rc ? rc : check_ov7670(b, sensor);
+}
+
+int64_t preview_bytes(const PreviewDst& d) { return (int64_t)d.out_h * d.out_ll; }
+
+// The last checks of a preview entry point before the lock: the preview-output
+// geometry d.  `buffers`: every buffer the call needs is there.  The object
 // sensor's call (ball) also checks its sums_pitch and words its errors itself.
-int32_t check_preview_out(const TrikHsvFrameBatch* b, int32_t ow, int32_t oh, int32_t oll, int64_t stride,
-                          bool buffers, int64_t* pb, bool ball = false, int32_t sums_pitch = 1) {
-  if (ow < 0 || oh < 0 || oll < 2 * ow || sums_pitch < 1)
+int32_t check_preview_out(const TrikHsvFrameBatch* b, const PreviewDst& d, bool buffers, bool ball = false,
+                          int32_t sums_pitch = 1) {
+  if (d.out_w < 0 || d.out_h < 0 || d.out_ll < 2 * d.out_w || sums_pitch < 1)
     return fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("preview geometry: need out_line_length >= 2*out_width") +
                                               (ball ? ", sums_pitch >= 1" : ""));
-  *pb = (int64_t)oh * oll;
-  if (b->n_frames > 1 && stride < *pb)
+  if (b->n_frames > 1 && d.stride < preview_bytes(d))
     return fail(TRIK_IVIDTRANSCODE_EFAIL, "preview_stride smaller than one preview");
-  if (b->n_frames > 0 && *pb > 0 && !buffers)
+  if (b->n_frames > 0 && preview_bytes(d) > 0 && !buffers)
     return fail(TRIK_IVIDTRANSCODE_EFAIL, ball ? "previews is NULL" : "NULL buffer");
+  return 0;
+}
+
+// A preview entry point after its checks: with the handle locked and its device
+// current, nothing when there is no frame or no preview byte; else the
+// previews checked as memory of that device, then `enqueue`.
+template <typename Enqueue>
+int32_t locked_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, const PreviewDst& d,
+                       Enqueue enqueue) {
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  if (b->n_frames == 0 || preview_bytes(d) == 0) return 0;
+  const int32_t rc = check_device(h, b, d.previews);
+  return rc ? rc : enqueue();
+}
+
+// Frames without pixels write no preview pixel: the zero fill alone.
+int32_t zero_previews(const TrikHsvFrameBatch* b, const PreviewDst& d, hipStream_t s) {
+  for (int32_t f = 0; f < b->n_frames; ++f)
+    HIP_TRY(hipMemsetAsync(d.previews + (int64_t)f * (b->n_frames > 1 ? d.stride : 0), 0, (size_t)preview_bytes(d), s));
+  return 0;
+}
+
+// Frames without pixels hold no blob: every slot's targets (and top, n_labels) zero.
+int32_t zero_blob_outputs(TrikHsvTarget* targets, int32_t* top, int32_t* n_labels, size_t slots, hipStream_t s) {
+  HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * 8 * slots, s));
+  if (top) HIP_TRY(hipMemsetAsync(top, 0, sizeof(int32_t) * 24 * slots, s));
+  if (n_labels) HIP_TRY(hipMemsetAsync(n_labels, 0, sizeof(int32_t) * slots, s));
   return 0;
 }
 
@@ -162,20 +197,12 @@ extern "C" int32_t trik_hsv_batch_preview(TRIK_VIDTRANSCODE_CV_Handle h, const T
                                           int32_t out_width, int32_t out_height,
                                           int32_t out_line_length, uint8_t* previews,
                                           int64_t preview_stride, void* stream) {
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
   int32_t rc = check_common(h, b, range, 1, sums);
-  if (rc) return rc;
-  int64_t pb = 0;
-  rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews != nullptr, &pb, true,
-                         sums_pitch);
+  if (!rc) rc = check_preview_out(b, d, previews != nullptr, true, sums_pitch);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lock(h->mu);
-  DeviceGuard dg(h->device);
-  if (b->n_frames == 0 || pb == 0) return 0;
-  rc = check_device(h, b, previews);
-  if (rc) return rc;
-  return preview_core(h, *b, *range, sums, sums_pitch, out_width, out_height, out_line_length, previews,
-                      preview_stride, s);
+  return locked_preview(h, b, d, [&] { return preview_core(h, *b, *range, sums, sums_pitch, d, s); });
 }
 
 extern "C" int32_t trik_hsv_batch_auto_range(const TrikHsvFrameBatch* b, uint16_t* out, void* stream) {
@@ -302,27 +329,21 @@ extern "C" int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle h, const Tr
                                          int32_t val_from, int32_t val_to, const TrikHsvTargetSums* sums,
                                          int32_t out_width, int32_t out_height, int32_t out_line_length,
                                          uint8_t* previews, int64_t preview_stride, void* stream) {
-  int32_t rc = check_handle_batch(h, b);
-  if (!rc) rc = check_ov7670(b, "line");
-  int64_t pb = 0;
-  if (!rc) rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && sums, &pb);
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
+  int32_t rc = check_ov7670_call(h, b, "line");
+  if (!rc) rc = check_preview_out(b, d, previews && sums);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lock(h->mu);
-  DeviceGuard dg(h->device);
-  if (b->n_frames == 0 || pb == 0) return 0;
-  rc = check_device(h, b, previews);
-  if (rc) return rc;
-  return line_preview_core(h, *b, line_alg(val_from, val_to), 5, b->width - 5, 1, sums, out_width, out_height,
-                           out_line_length, previews, preview_stride, s);
+  return locked_preview(h, b, d, [&] {
+    return line_preview_core(h, *b, line_alg(val_from, val_to), 5, b->width - 5, 1, sums, d, s);
+  });
 }
 
 extern "C" int32_t trik_hsv_blob_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
                                        const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg* hsv, TrikHsvTarget* targets,
                                        int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,
                                        void* stream) {
-  int32_t r = check_handle_batch(h, b);
-  if (!r) r = check_ov7670(b, "multi-blob");
+  int32_t r = check_ov7670_call(h, b, "multi-blob");
   if (r) return r;
   if (!hsv) return fail(TRIK_IVIDTRANSCODE_EFAIL, "hsv is NULL");
   if (b->width % 32 || b->height % 4) return fail(TRIK_IVIDTRANSCODE_EFAIL, "width % 32 / height % 4");
@@ -335,12 +356,7 @@ extern "C" int32_t trik_hsv_blob_batch(TRIK_VIDTRANSCODE_CV_Handle h, const Trik
   if (b->n_frames == 0) return 0;
   r = check_device(h, b, targets);
   if (r) return r;
-  if (b->width == 0 || b->height == 0) {
-    HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * 8 * (size_t)b->n_frames, s));
-    if (top) HIP_TRY(hipMemsetAsync(top, 0, sizeof(int32_t) * 24 * (size_t)b->n_frames, s));
-    if (n_labels) HIP_TRY(hipMemsetAsync(n_labels, 0, sizeof(int32_t) * (size_t)b->n_frames, s));
-    return 0;
-  }
+  if (b->width == 0 || b->height == 0) return zero_blob_outputs(targets, top, n_labels, (size_t)b->n_frames, s);
   BlobArgs ba;
   return blob_core(h, *b, blob_range_args(*hsv), targets, top, meta, labels, n_labels, s, ba);
 }
@@ -361,13 +377,8 @@ extern "C" int32_t trik_hsv_blob_batch_ranges(TRIK_VIDTRANSCODE_CV_Handle h, con
   if (b->n_frames == 0) return 0;
   r = check_device(h, b, targets);
   if (r) return r;
-  if (b->width == 0 || b->height == 0) {
-    const size_t slots = (size_t)b->n_frames * (size_t)n;
-    HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * 8 * slots, s));
-    if (top) HIP_TRY(hipMemsetAsync(top, 0, sizeof(int32_t) * 24 * slots, s));
-    if (n_labels) HIP_TRY(hipMemsetAsync(n_labels, 0, sizeof(int32_t) * slots, s));
-    return 0;
-  }
+  if (b->width == 0 || b->height == 0)
+    return zero_blob_outputs(targets, top, n_labels, (size_t)b->n_frames * (size_t)n, s);
   return blob_ranges_core(h, *b, ranges, n, targets, top, meta, labels, n_labels, s);
 }
 
@@ -383,25 +394,17 @@ extern "C" int32_t trik_hsv_blob_preview(TRIK_VIDTRANSCODE_CV_Handle h, const Tr
                                          const uint8_t* meta, const int32_t* top, int32_t out_width,
                                          int32_t out_height, int32_t out_line_length, uint8_t* previews,
                                          int64_t preview_stride, void* stream) {
-  int32_t rc = check_handle_batch(h, b);
-  if (!rc) rc = check_ov7670(b, "multi-blob");
-  int64_t pb = 0;
-  if (!rc)
-    rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && meta && top, &pb);
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
+  int32_t rc = check_ov7670_call(h, b, "multi-blob");
+  if (!rc) rc = check_preview_out(b, d, previews && meta && top);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lock(h->mu);
-  DeviceGuard dg(h->device);
-  if (b->n_frames == 0 || pb == 0) return 0;
-  rc = check_device(h, b, previews);
-  if (rc) return rc;
-  return blob_preview_core(h, *b, meta, top, out_width, out_height, out_line_length, previews, preview_stride, s);
+  return locked_preview(h, b, d, [&] { return blob_preview_core(h, *b, meta, top, d, s); });
 }
 
 extern "C" int32_t trik_hsv_mxn_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, int32_t rows_m,
                                       int32_t cols_n, int32_t* colors, uint16_t* bins, void* stream) {
-  int32_t r = check_handle_batch(h, b);
-  if (!r) r = check_ov7670(b, "MxN");
+  int32_t r = check_ov7670_call(h, b, "MxN");
   if (r) return r;
   const std::string e = mxn_grid_error(rows_m, cols_n);
   if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
@@ -425,27 +428,18 @@ extern "C" int32_t trik_hsv_mxn_preview(TRIK_VIDTRANSCODE_CV_Handle h, const Tri
                                         int32_t cols_n, const int32_t* colors, int32_t out_width,
                                         int32_t out_height, int32_t out_line_length, uint8_t* previews,
                                         int64_t preview_stride, void* stream) {
-  int32_t rc = check_handle_batch(h, b);
-  if (!rc) rc = check_ov7670(b, "MxN");
+  int32_t rc = check_ov7670_call(h, b, "MxN");
   if (rc) return rc;
   const std::string e = mxn_grid_error(rows_m, cols_n);
   if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
-  int64_t pb = 0;
-  rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && colors, &pb);
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
+  rc = check_preview_out(b, d, previews && colors);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lock(h->mu);
-  DeviceGuard dg(h->device);
-  if (b->n_frames == 0 || pb == 0) return 0;
-  rc = check_device(h, b, previews);
-  if (rc) return rc;
-  if (b->width == 0 || b->height == 0) {  // no pixel to write: the zero fill alone
-    for (int32_t f = 0; f < b->n_frames; ++f)
-      HIP_TRY(hipMemsetAsync(previews + (int64_t)f * (b->n_frames > 1 ? preview_stride : 0), 0, (size_t)pb, s));
-    return 0;
-  }
-  return mxn_preview_core(h, *b, rows_m, cols_n, colors, out_width, out_height, out_line_length, previews,
-                          preview_stride, s);
+  return locked_preview(h, b, d, [&] {
+    if (b->width == 0 || b->height == 0) return zero_previews(b, d, s);
+    return mxn_preview_core(h, *b, rows_m, cols_n, colors, d, s);
+  });
 }
 
 extern "C" uint32_t trik_hsv_mxn_color(int32_t h_bin, int32_t s_bin, int32_t v_bin) {
@@ -480,29 +474,20 @@ extern "C" int32_t trik_hsv_edge_preview(TRIK_VIDTRANSCODE_CV_Handle h, const Tr
                                          int32_t threshold, const TrikHsvTargetSums* sums, int32_t out_width,
                                          int32_t out_height, int32_t out_line_length, uint8_t* previews,
                                          int64_t preview_stride, void* stream) {
-  int32_t rc = check_handle_batch(h, b);
-  if (!rc) rc = check_ov7670(b, "edge-line");
+  int32_t rc = check_ov7670_call(h, b, "edge-line");
   if (rc) return rc;
   const std::string e = edge_geometry_error(b->width, b->height, b->line_length);
   if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
   if (threshold < 0 || threshold > 255)
     return fail(TRIK_IVIDTRANSCODE_EFAIL, "edge_preview: threshold must be 0..255");
-  int64_t pb = 0;
-  rc = check_preview_out(b, out_width, out_height, out_line_length, preview_stride, previews && sums, &pb);
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
+  rc = check_preview_out(b, d, previews && sums);
   if (rc) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  std::lock_guard<std::mutex> lock(h->mu);
-  DeviceGuard dg(h->device);
-  if (b->n_frames == 0 || pb == 0) return 0;
-  rc = check_device(h, b, previews);
-  if (rc) return rc;
-  if (b->width == 0 || b->height == 0) {  // no pixel to write: the zero fill alone
-    for (int32_t f = 0; f < b->n_frames; ++f)
-      HIP_TRY(hipMemsetAsync(previews + (int64_t)f * (b->n_frames > 1 ? preview_stride : 0), 0, (size_t)pb, s));
-    return 0;
-  }
-  return edge_preview_core(h, *b, threshold, sums, out_width, out_height, out_line_length, previews, preview_stride,
-                           s);
+  return locked_preview(h, b, d, [&] {
+    if (b->width == 0 || b->height == 0) return zero_previews(b, d, s);
+    return edge_preview_core(h, *b, threshold, sums, d, s);
+  });
 }
 
 // ESEQ:397-417 on the host, as edge_targets_kernel on the device
@@ -527,8 +512,7 @@ extern "C" int32_t trik_hsv_edge_targets(const TrikHsvTargetSums* sums, int32_t 
 extern "C" int32_t trik_hsv_jpeg_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b, int32_t quality,
                                        int32_t black_and_white, uint8_t* out, int64_t out_stride,
                                        int64_t out_capacity, uint32_t* sizes, int16_t* coeffs, void* stream) {
-  int32_t r = check_handle_batch(h, b);
-  if (!r) r = check_ov7670(b, "JPEG");
+  int32_t r = check_ov7670_call(h, b, "JPEG");
   if (r) return r;
   const std::string e = jpeg_geometry_error(b->width, b->height);
   if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);

@@ -89,7 +89,7 @@ void blob_meta_kernel(BlobArgs a, MetaGeom g) {
     if (valid) {
       const uint32_t f = fdiv(m, g.per_frame), rem = m - f * g.per_frame.d;
       const uint32_t mr = fdiv(rem, g.per_row), mc = rem - mr * bw;
-      const uint8_t* yp = a.frames + (int64_t)f * a.frame_stride + (int64_t)(4 * mr + rr) * ll + 4 * mc;
+      const uint8_t* yp = frame_ptr(a, f) + (int64_t)(4 * mr + rr) * ll + 4 * mc;
       const uint8_t* cp = yp + (int64_t)a.height * ll;
       uint32_t yy, cc;
       if (a.aligned4) {
@@ -157,7 +157,7 @@ void blob_meta_ranges_kernel(BlobArgs a, MetaGeom g, RangeGroup rg) {
     if (valid) {
       const uint32_t f = fdiv(m, g.per_frame), rem = m - f * g.per_frame.d;
       const uint32_t mr = fdiv(rem, g.per_row), mc = rem - mr * bw;
-      const uint8_t* row = a.frames + (int64_t)f * a.frame_stride + (int64_t)(4 * mr + rr) * ll;
+      const uint8_t* row = frame_ptr(a, f) + (int64_t)(4 * mr + rr) * ll;
       uint32_t w0, w1;
       if (LAYOUT == TRIK_HSV_LAYOUT_YUYV) {
         const uint8_t* p = row + 8 * mc;

@@ -831,7 +831,7 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
     const int r0 = trem * g.rstep * g.steps;
     const int y0 = r0 + ro;
     const int steps = trem == g.tiles_per_frame - 1 ? g.steps_last : g.steps;
-    const uint8_t* p = a.frames + (int64_t)f * a.frame_stride + (int64_t)y0 * a.line_length + col_bytes;
+    const uint8_t* p = frame_ptr(a, f) + (int64_t)y0 * a.line_length + col_bytes;
 
     uint32_t P[CW], O = 0, Q = 0, CumS = 0, CumA = 0, CumB = 0;
 #pragma unroll
@@ -944,7 +944,7 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
     };
 
     // a row inside the frame for lanes whose rows run past it (re-read, masked)
-    const uint8_t* pf = active && y0 < a.height ? p : a.frames + (int64_t)f * a.frame_stride + col_bytes;
+    const uint8_t* pf = active && y0 < a.height ? p : frame_ptr(a, f) + col_bytes;
     // steps whose first (second) piece row lies inside the frame
     const bool full = (r0 + steps * g.rstep <= a.height) && (g.k * g.cpr) % 64 == 0;
     // (only partial tiles need them: the divisions run on the VALU)
@@ -953,7 +953,7 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
       vsteps = active ? max(0, min(steps, (a.height - y0 + g.rstep - 1) / g.rstep)) : 0;
       vstepsb = active ? max(0, min(steps, (a.height - y0 - half + g.rstep - 1) / g.rstep)) : 0;
     }
-    const uint8_t* tbase = a.frames + (int64_t)f * a.frame_stride + (int64_t)r0 * a.line_length;
+    const uint8_t* tbase = frame_ptr(a, f) + (int64_t)r0 * a.line_length;
     auto run = [&](auto full_c) {
       constexpr bool FULL = decltype(full_c)::value;
       // the two pieces' meta words without their flag bits (bits 0-3 are 0),
@@ -1288,7 +1288,7 @@ __global__ __launch_bounds__(kMaxBlock) void blob_chroma_meta_kernel(BlobArgs a,
     const uint32_t rem = it - r.f * g.per_frame.d;
     r.mr = fdiv(rem, g.per_row);
     r.ch = rem - r.mr * g.per_row.d;
-    r.p = a.frames + (int64_t)r.f * a.frame_stride + (int64_t)(4 * r.mr) * ll + 16 * (int64_t)r.ch;
+    r.p = frame_ptr(a, r.f) + (int64_t)(4 * r.mr) * ll + 16 * (int64_t)r.ch;
     return r;
   };
   Item cur = item_at(base, Item{a.frames, 0u, 0u, 0u, false});

@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kEdgeBlock) void edge_vec_kernel(EdgeArgs a, EdgeGe
   const bool live = live_group && gl < g.lanes_per_row;
   const int w = a.width;
   const int c0 = live ? gl * 4 * Q : 0;  // (idle lanes read columns 0 .. 4Q-1 and count nothing)
-  const uint8_t* p = a.frames + (int64_t)f * a.frame_stride + (int64_t)r0 * w + c0;
+  const uint8_t* p = frame_ptr(a, f) + (int64_t)r0 * w + c0;
 
   u16x2 mask[G], colpk[G];
 #pragma unroll
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kEdgeBlock) void edge_vec_kernel(EdgeArgs a, EdgeGe
 __global__ __launch_bounds__(kEdgeBlock) void edge_map_kernel(EdgeArgs a) {
   __shared__ uint32_t red[2][kEdgeBlock / 64];
   const int f = blockIdx.x / a.height, r = blockIdx.x - f * a.height;
-  const uint8_t* in = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* in = frame_ptr(a, f);
   const int w = a.width;
   const int64_t last = (int64_t)w * (a.height - 2) - 3;
   uint32_t n = 0, sx = 0;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void edge_preview_kernel(EdgePreviewArgs a, ui
     const int sr = a.last_row[ro], sc = a.last_col[x];
     if (sr >= 0 && sc >= 0) {
       const int w = a.width, h = a.height;
-      const uint8_t* in = a.frames + (int64_t)f * a.frame_stride;
+      const uint8_t* in = frame_ptr(a, f);
       const int64_t i = (int64_t)sr * w + sc;
       const int y = (int)edge_byte(in, w, i, (int64_t)w * (h - 2) - 3, a.threshold);
       const uint8_t* cbcr = in + (int64_t)w * h + 2 * (i >> 1);  // cb = byte 2k, cr = byte 2k + 1 (ESEQ:166-173)
@@ -398,8 +398,7 @@ int launch_edge_preview(const EdgePreviewArgs& a, hipStream_t s) {
   const int64_t per_launch = kMaxBlocks / per_frame;
   for (int64_t f0 = 0; f0 < a.n_frames; f0 += per_launch) {
     EdgePreviewArgs b = a;
-    b.n_frames = (int32_t)(a.n_frames - f0 < per_launch ? a.n_frames - f0 : per_launch);
-    b.frames = a.frames + f0 * a.frame_stride;
+    b.narrow(f0, a.n_frames - f0 < per_launch ? a.n_frames - f0 : per_launch);
     b.sums = a.sums + f0;
     b.previews = a.previews + f0 * a.preview_stride;
     hipLaunchKernelGGL(edge_preview_kernel, dim3((unsigned)(b.n_frames * per_frame)), dim3(256), 0, s, b, bpr);

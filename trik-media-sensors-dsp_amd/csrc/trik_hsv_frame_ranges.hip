@@ -43,10 +43,7 @@ constexpr int kFrTargetBlocks = 2048;
 // a launch holds fewer than 2^32 threads: larger batches go in several launches
 constexpr int64_t kFrMaxLaunchBlocks = 0xFFFFFFFFll / kFrBlock;
 
-struct FrameRangesArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length;
+struct FrameRangesArgs : FrameView {
   int32_t n_ranges;
   int32_t segs, seg_rows;   // bands per frame, rows per band
   FastDiv units_per_row;    // width / 8
@@ -178,7 +175,7 @@ __global__ __launch_bounds__(kFrBlock) void frame_ranges_kernel(FrameRangesArgs 
   }
   __syncthreads();
 
-  const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* fr = frame_ptr(a, f);
   const int r0 = seg * a.seg_rows;
   const int rows = min(a.seg_rows, a.height - r0);
   const uint32_t units = (uint32_t)rows * a.units_per_row.d;  // < 2^27
@@ -242,10 +239,8 @@ void launch_frame_ranges_layout(int align, unsigned blocks, hipStream_t s, const
 // a validated batch with width, height and n_frames > 0.
 int launch_frame_ranges(const TrikHsvFrameBatch& b, const uint16_t* ranges, int n_ranges, TrikHsvTargetSums* sums,
                         hipStream_t s) {
-  FrameRangesArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.n_frames > 1 ? b.frame_stride : 0;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  FrameRangesArgs a = {frame_view(b)};
+  if (b.n_frames <= 1) a.frame_stride = 0;  // (a single frame's stride is not validated: it counts as aligned)
   a.n_ranges = n_ranges;
   a.units_per_row = make_div((uint32_t)b.width / 8u);
   // the widest load every address of the batch is aligned for
@@ -264,8 +259,7 @@ int launch_frame_ranges(const TrikHsvFrameBatch& b, const uint16_t* ranges, int 
   const int64_t per_launch = kFrMaxLaunchBlocks / a.segs;  // frames
   for (int64_t f0 = 0; f0 < b.n_frames; f0 += per_launch) {
     FrameRangesArgs c = a;
-    c.n_frames = (int32_t)(b.n_frames - f0 < per_launch ? b.n_frames - f0 : per_launch);
-    c.frames = a.frames + f0 * a.frame_stride;
+    c.narrow(f0, b.n_frames - f0 < per_launch ? b.n_frames - f0 : per_launch);
     c.ranges = ranges + f0 * n_ranges * 6;
     c.sums = sums + f0 * n_ranges;
     const unsigned blocks = (unsigned)((int64_t)c.n_frames * a.segs);

@@ -396,16 +396,21 @@ AutoRangeArgs auto_range_args(const TrikHsvFrameBatch& b, uint16_t* out);
 // the exact-search detectors (kind and geometry validated: auto_exact_error)
 AutoExactArgs auto_exact_args(const TrikHsvFrameBatch& b, int kind, int32_t* scores, int32_t* start, uint16_t* out,
                               int32_t* best);
+// Where a preview call writes: the previews' geometry, the device buffer and
+// the bytes from one frame's preview to the next.
+struct PreviewDst {
+  int32_t out_w, out_h, out_ll;
+  uint8_t* previews;
+  int64_t stride;
+};
 // the object sensor's preview: body, guide lines and the circle from sums
 int32_t preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
-                     const TrikHsvTargetSums* sums, int sums_pitch, int ow, int oh, int oll, uint8_t* previews,
-                     int64_t stride, hipStream_t s);
+                     const TrikHsvTargetSums* sums, int sums_pitch, const PreviewDst& d, hipStream_t s);
 // a line sensor's preview: source columns col_lo..col_hi write, the tables are
 // table_range's; band = 1 draws the ov7670 line sensor's band lines
 int32_t line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
                           const TRIK_VIDTRANSCODE_CV_InArgsAlg& table_range, int col_lo, int col_hi, int band,
-                          const TrikHsvTargetSums* sums, int ow, int oh, int oll, uint8_t* previews,
-                          int64_t stride, hipStream_t s);
+                          const TrikHsvTargetSums* sums, const PreviewDst& d, hipStream_t s);
 // the multi-blob sensor; NULL outputs go to the handle's scratch (ba tells where)
 int32_t blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
                   TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,
@@ -417,7 +422,7 @@ int32_t blob_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK
                          int32_t* n_labels, hipStream_t s);
 // its preview: set metapixels, guide lines, target marks
 int32_t blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta, const int32_t* top,
-                          int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);
+                          const PreviewDst& d, hipStream_t s);
 
 // the MxN sensor: cell colours (and winning bins when not NULL) of rows_m x
 // cols_n cells per frame; rows_m, cols_n validated by the caller (mxn_grid_error)
@@ -425,7 +430,7 @@ int32_t mxn_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int co
                  uint16_t* bins, hipStream_t s);
 // its preview: every source pixel, then the cells' 20x20 squares in cell order
 int32_t mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int cols_n, const int32_t* colors,
-                         int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);
+                         const PreviewDst& d, hipStream_t s);
 // "" when 1 <= rows_m, 1 <= cols_n and rows_m * cols_n <= 100 (OutArgs holds
 // 100 colours; the reference does not check)
 std::string mxn_grid_error(int64_t rows_m, int64_t cols_n);
@@ -450,7 +455,7 @@ EdgeArgs edge_args(const TrikHsvFrameBatch& b, int threshold, TrikHsvTargetSums*
 // its preview: the thresholded map through IMG_ycbcr422pl_to_rgb565 with the
 // frame's chroma, every source pixel, then the target line (ESEQ:226-249, 405)
 int32_t edge_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int threshold, const TrikHsvTargetSums* sums,
-                          int ow, int oh, int oll, uint8_t* previews, int64_t stride, hipStream_t s);
+                          const PreviewDst& d, hipStream_t s);
 
 }  // namespace trik_hsv
 #pragma GCC visibility pop

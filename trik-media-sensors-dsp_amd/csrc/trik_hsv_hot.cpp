@@ -272,18 +272,15 @@ int32_t trik_hsv::run_sums(TrikCvHandle* h, const TrikHsvFrameBatch* b,
   const bool empty = b->n_frames == 0 || b->width == 0 || b->height == 0;
   const int groups = (n + kRangesPerLaunch - 1) / kRangesPerLaunch;
   const bool big = (int64_t)b->n_frames * b->width * b->height >= (int64_t)TRIK_HSV_CHROMA_MIN_PIXELS;
-  std::vector<KernelArgs> args(empty ? 0 : groups);
+  FrameView frames = frame_view(*b);
+  if (b->n_frames <= 1) frames.frame_stride = 0;  // (not validated then; the launchers test its alignment)
+  std::vector<KernelArgs> args(empty ? 0 : groups, KernelArgs{frames});
   std::vector<HotPlan> plans(args.size(), kPlanStripe);
   bool fused = step != nullptr && !masks && !empty;
   poll_measured(*t);
   bool reprobe = false;
   for (size_t g = 0; g < args.size(); ++g) {
     KernelArgs& a = args[g];
-    a.frames = static_cast<const uint8_t*>(b->frames);
-    a.frame_stride = b->n_frames > 1 ? b->frame_stride : 0;
-    a.n_frames = b->n_frames;
-    a.width = b->width; a.height = b->height; a.line_length = b->line_length;
-    a.layout = b->layout;
     a.n_ranges = n - (int)g * kRangesPerLaunch < kRangesPerLaunch ? n - (int)g * kRangesPerLaunch : kRangesPerLaunch;
     a.range_offset = (int)g * kRangesPerLaunch;
     a.sums_ranges = n;

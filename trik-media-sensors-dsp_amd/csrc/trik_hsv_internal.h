@@ -146,12 +146,45 @@ void compile_stripe_tables(const RangeTables& base, int n, StripeTables* out);
 enum DetectMode { kDetectFull = 0, kDetectSV = 1, kDetectV = 2 };
 int detect_mode(const RangeTables& t, int n);
 
-struct KernelArgs {
+// The frames of a batch as the kernels read them: the public TrikHsvFrameBatch
+// with a byte pointer.  Every kernel argument struct below derives from it, so
+// a sensor's host code fills them in one step (frame_view) and its kernels read
+// a.frames, a.width, ... directly.
+struct FrameView {
   const uint8_t* frames;
   int64_t frame_stride;
-  int32_t n_frames;
-  int32_t width, height, line_length;
-  int32_t layout;
+  int32_t n_frames, width, height, line_length, layout;
+  // narrows the view to its frames [first, first + count): a chunk of a batch
+  void narrow(int64_t first, int64_t count) {
+    if (first) frames += first * frame_stride;
+    n_frames = (int32_t)count;
+  }
+};
+// b's frames [first, first + count); count < 0: all from `first` on
+inline FrameView frame_view(const TrikHsvFrameBatch& b, int64_t first = 0, int64_t count = -1) {
+  FrameView v = {static_cast<const uint8_t*>(b.frames), b.frame_stride, b.n_frames, b.width, b.height,
+                 b.line_length, b.layout};
+  v.narrow(first, count < 0 ? b.n_frames - first : count);
+  return v;
+}
+template <typename F>
+__device__ __forceinline__ const uint8_t* frame_ptr(const FrameView& a, F f) {
+  return a.frames + (int64_t)f * a.frame_stride;
+}
+
+// Where a preview kernel writes and the handle's scale maps for that geometry
+// (preview_maps): the second base of the preview kernels' argument structs.
+struct PreviewTarget {
+  int32_t out_w, out_h, out_ll;
+  uint8_t* previews;
+  int64_t preview_stride;
+  const uint32_t* wi2wo;    // [width]  WSEQ:375-379
+  const uint32_t* hi2ho;    // [height] WSEQ:381-385
+  const int32_t* last_row;  // [out_h]: last source row mapped to each output row, or -1
+  const int32_t* last_col;  // [out_w]
+};
+
+struct KernelArgs : FrameView {
   int32_t n_ranges;      // ranges in this launch (1..4)
   int32_t range_offset;  // index of this launch's first range in the sums array
   int32_t sums_ranges;   // ranges per frame in the sums array (row pitch)
@@ -226,20 +259,10 @@ __device__ __forceinline__ bool gated_out(const unsigned long long* gate, unsign
 constexpr unsigned long long kChromaMaxCost = (unsigned long long)(TRIK_HSV_CHROMA_MAX_SHARE * 4294967296.0);
 
 // RGB565X preview of N frames for one range (trik_hsv_operator.hip).
-struct PreviewArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length, layout;
+struct PreviewArgs : FrameView, PreviewTarget {
   PackedRange range;          // the preview's range (WSEQ:425-445)
   const StripeTables* tables = nullptr;  // that range compiled as range 0 (device)
   int32_t aligned4;           // frames, strides, line lengths and previews 4-byte aligned
-  int32_t out_w, out_h, out_ll;
-  uint8_t* previews;
-  int64_t preview_stride;
-  const int32_t* last_row;  // [out_h]: last source row mapped to each output row, or -1
-  const int32_t* last_col;  // [out_w]
-  const uint32_t* wi2wo;    // [width]  WSEQ:375-379
-  const uint32_t* hi2ho;    // [height] WSEQ:381-385
   // ov7670 multi-blob preview: when set, a pixel is "detected" iff its 4x4
   // metapixel is set ([n][H/4][W/4], OSEQ:411-413) instead of by `range`
   const uint8_t* meta = nullptr;
@@ -269,10 +292,7 @@ struct PreviewArgs {
 
 // Auto HSV range of N frames (trik_hsv_operator.hip); out[f][6] = detectHue,
 // detectHueTolerance, detectSat, detectSatTolerance, detectVal, detectValTolerance.
-struct AutoRangeArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length, layout;
+struct AutoRangeArgs : FrameView {
   int32_t c_lo, c_hi, r_lo, r_hi;  // exclusive zone bounds (uint16 values, hpp:88-108)
   int32_t aligned4;                // frames, stride and line length 4-byte aligned
   uint16_t* out;
@@ -286,10 +306,7 @@ struct AutoRangeArgs {
 // or row > nr_hi.
 constexpr int kAutoObjectBins = 32 * 32;
 constexpr int kAutoLineBins = 256;
-struct AutoExactArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length, layout;
+struct AutoExactArgs : FrameView {
   int32_t kind;  // TRIK_HSV_AUTO_*
   int32_t pc_lo, pc_hi, pr_lo, pr_hi;
   int32_t nc_lo, nc_hi, nr_lo, nr_hi;
@@ -340,10 +357,7 @@ __host__ __device__ inline void auto_range_scale(int kind, int h1, int h2, int s
 
 // ov7670 line sensor of N frames (trik_hsv_line.hip).  sums[f] = {N, sumX,
 // crossPoints} (crossPoints in the sum_y slot), zeroed by the caller.
-struct LineArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length;
+struct LineArgs : FrameView {
   uint32_t val_lo, val_hi;           // scaled V bounds (LSEQ:397-398)
   int32_t band_start, band_stop;     // cross-point rows (LSEQ:298)
   TrikHsvTargetSums* sums;
@@ -425,10 +439,7 @@ int launch_preview_rows2(const PreviewArgs& a, hipStream_t s);
 int launch_line_preview(PreviewArgs a, const TrikHsvTargetSums* sums, int band, hipStream_t s);
 
 // ov7670 multi-blob sensor of N frames (trik_hsv_blob.hip).
-struct BlobArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length;
+struct BlobArgs : FrameView {
   PackedRange range;         // the sticky BitmapBuilder range (BMB:62-77)
   const StripeTables* tables;  // that range compiled as range 0 (device)
   int32_t aligned4;          // frames, stride and line length 4-byte aligned
@@ -473,10 +484,7 @@ int launch_blob_overlay(const PreviewArgs& a, const int32_t* top, hipStream_t s)
 // ov7670 MxN colour-grid sensor of N frames (trik_hsv_mxn.hip).
 // rows_m is the reference's InArgs widthM (cell rows), cols_n its heightN
 // (cell columns): MSEQ:585-588 crosses the names.
-struct MxnArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length;
+struct MxnArgs : FrameView {
   int32_t rows_m, cols_n;
   int32_t row_step, col_step;  // height / rows_m, width / cols_n (truncated; 0: empty cells)
   int32_t aligned4;            // frames, stride and line length 4-byte aligned
@@ -484,19 +492,9 @@ struct MxnArgs {
   int32_t* colors;             // [n][rows_m * cols_n]
   uint16_t* bins;              // optional [n][rows_m * cols_n]: h << 4 | s << 2 | v
 };
-struct MxnPreviewArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length;
+struct MxnPreviewArgs : FrameView, PreviewTarget {
   int32_t rows_m, cols_n, row_step, col_step;
   const int32_t* colors;  // [n][rows_m * cols_n]
-  int32_t out_w, out_h, out_ll;
-  uint8_t* previews;
-  int64_t preview_stride;
-  const uint32_t* wi2wo;    // [width]  (preview_maps)
-  const uint32_t* hi2ho;    // [height]
-  const int32_t* last_row;  // [out_h]
-  const int32_t* last_col;  // [out_w]
 };
 int launch_mxn(const MxnArgs& a, hipStream_t s);
 int launch_mxn_preview(const MxnPreviewArgs& a, hipStream_t s);
@@ -511,28 +509,15 @@ const uint32_t* mxn_color_table();
 // zeroed by the caller; each row's count and column sum wrap mod 65536
 // (ESEQ:160-161, 203-204).
 constexpr int kEdgeMaxSide = 2048;  // width and height (the ov7670 object sensor's cap)
-struct EdgeArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height;
+struct EdgeArgs : FrameView {
   int32_t threshold;  // 0..255 (50 in the codec, ESEQ:183)
   TrikHsvTargetSums* sums;
   TrikHsvTarget* targets;  // may be NULL
   uint8_t* edges;          // optional [n][height][width]: the thresholded map
 };
-struct EdgePreviewArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height;
+struct EdgePreviewArgs : FrameView, PreviewTarget {
   int32_t threshold;
   const TrikHsvTargetSums* sums;  // [n]: the target line's column
-  int32_t out_w, out_h, out_ll;
-  uint8_t* previews;
-  int64_t preview_stride;
-  const uint32_t* wi2wo;    // [width]  (preview_maps)
-  const uint32_t* hi2ho;    // [height]
-  const int32_t* last_row;  // [out_h]
-  const int32_t* last_col;  // [out_w]
 };
 // sums (and the map when a.edges is set), then the targets when a.targets is set
 int launch_edge(const EdgeArgs& a, hipStream_t s);
@@ -560,10 +545,7 @@ struct JpegHeader {
   uint8_t bytes[kJpegMaxHeader];
   int32_t size;
 };
-struct JpegArgs {
-  const uint8_t* frames;
-  int64_t frame_stride;
-  int32_t n_frames, width, height, line_length;
+struct JpegArgs : FrameView {
   int32_t aligned4;
   int32_t ncomp;               // 3, or 1 in black and white
   int32_t blocks_w;            // width / 8

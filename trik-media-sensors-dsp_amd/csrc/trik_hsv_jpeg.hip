@@ -116,7 +116,7 @@ __global__ __launch_bounds__(kDuBlock) void jpeg_block_kernel(JpegArgs a, JpegDi
   // c / 2 of the chroma row, U its odd byte, V its even byte (JENC:745-748).
   int d[64];
   const int64_t ll = a.line_length;
-  const uint8_t* p = a.frames + (int64_t)x.frame * a.frame_stride + (x.comp ? ll * a.height : 0) +
+  const uint8_t* p = frame_ptr(a, x.frame) + (x.comp ? ll * a.height : 0) +
                      (int64_t)x.by * 8 * ll + x.bx * 8;
 #pragma unroll
   for (int r = 0; r < 8; ++r) {

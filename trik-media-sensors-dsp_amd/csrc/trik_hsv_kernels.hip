@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(KernelArgs a, int64_t n_
     const int r0 = (int)(t - (int64_t)f * tiles_per_frame) * band;
     const int rows = min(band, a.height - r0);
     const int n = rows * cpr;
-    const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+    const uint8_t* fr = frame_ptr(a, f);
     for (int i = threadIdx.x; i < n; i += kBlock) {
       const int row = i / cpr, col = i - row * cpr;
       const int y = r0 + row;

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(1024) void line_vec_kernel(LineArgs a, LineGeom g) 
     const int b_hi = (int)max((int64_t)b_lo, min(be64, (int64_t)row_end));
     const int base = row0 + r_off;
     const int64_t ll = a.line_length;
-    const uint8_t* yp = a.frames + (int64_t)f * a.frame_stride + (int64_t)base * ll + 8 * unit;
+    const uint8_t* yp = frame_ptr(a, f) + (int64_t)base * ll + 8 * unit;
     const int64_t cofs = (int64_t)a.height * ll, step = (int64_t)g.rpi * ll;
     const u16x2 mlo = (u16x2)(unsigned short)g.mlo;
     const u16x2 kspan = (u16x2)g.kspan;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kLineBlock) void line_sums_kernel(LineArgs a) {
   const int groups = (a.height + kLineRows - 1) / kLineRows;
   const int f = blockIdx.x / groups;
   const int r0 = (blockIdx.x - f * groups) * kLineRows;
-  const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* fr = frame_ptr(a, f);
   const int pairs = a.width / 2;
   uint32_t n = 0, sx = 0, cross = 0;
   for (int i = threadIdx.x; i < kLineRows * pairs; i += blockDim.x) {

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kMxnBlock) void mxn_hist_kernel(MxnArgs a, MxnGeom 
   // one 32-bit load per plane); pixels of a group outside the cell's columns
   // are skipped.  A wave takes 64 consecutive groups in raster order.
   const int g0 = c0 >> 2;
-  const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* fr = frame_ptr(a, f);
   const int64_t ll = a.line_length, cofs = ll * a.height;
   for (uint32_t q0 = (uint32_t)wave * 64u; q0 < g.total; q0 += kMxnWaves * 64u) {
     const uint32_t q = q0 + (uint32_t)lane;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void mxn_preview_kernel(MxnPreviewArgs a, uint
     const int sr = a.last_row[ro], sc = a.last_col[x];
     if (sr >= 0 && sc >= 0) {
       int Y, U, V;
-      fetch_yuv(a.frames + (int64_t)f * a.frame_stride, a.height, a.line_length, TRIK_HSV_LAYOUT_OV7670, sr, sc, Y,
+      fetch_yuv(frame_ptr(a, f), a.height, a.line_length, TRIK_HSV_LAYOUT_OV7670, sr, sc, Y,
                 U, V);
       uint32_t rgb = pixel_rgb(Y, U, V).rgb888();
       const int ci = mxn_square_cell(ro, a.rows_m, a.row_step, a.height, a.hi2ho);
@@ -242,8 +242,7 @@ int launch_mxn(const MxnArgs& a, hipStream_t s) {
   const int64_t per_launch = kMaxLaunchBlocks / cells;  // frames (cells <= 100)
   for (int64_t f0 = 0; f0 < a.n_frames; f0 += per_launch) {
     MxnArgs b = a;
-    b.n_frames = (int32_t)(a.n_frames - f0 < per_launch ? a.n_frames - f0 : per_launch);
-    b.frames = a.frames + f0 * a.frame_stride;
+    b.narrow(f0, a.n_frames - f0 < per_launch ? a.n_frames - f0 : per_launch);
     b.colors = a.colors + f0 * cells;
     if (a.bins) b.bins = a.bins + f0 * cells;
     hipLaunchKernelGGL(mxn_hist_kernel, dim3((unsigned)(b.n_frames * cells)), dim3(kMxnBlock), 0, s, b, g);
@@ -261,8 +260,7 @@ int launch_mxn_preview(const MxnPreviewArgs& a, hipStream_t s) {
   const int64_t per_launch = kMaxLaunchBlocks / per_frame;
   for (int64_t f0 = 0; f0 < a.n_frames; f0 += per_launch) {
     MxnPreviewArgs b = a;
-    b.n_frames = (int32_t)(a.n_frames - f0 < per_launch ? a.n_frames - f0 : per_launch);
-    b.frames = a.frames + f0 * a.frame_stride;
+    b.narrow(f0, a.n_frames - f0 < per_launch ? a.n_frames - f0 : per_launch);
     b.colors = a.colors + f0 * a.rows_m * a.cols_n;
     b.previews = a.previews + f0 * a.preview_stride;
     hipLaunchKernelGGL(mxn_preview_kernel, dim3((unsigned)(b.n_frames * per_frame)), dim3(256), 0, s, b, bpr);

@@ -104,7 +104,7 @@ void preview_gather_kernel(PreviewArgs a, PreviewGeom g) {
     uint32_t w[kQ][2];  // each pixel as a YUYV word with its Y in byte 0
 #pragma unroll
     for (int u = 0; u < kQ; ++u) {
-      const uint8_t* fr = a.frames + (int64_t)ff[u] * a.frame_stride;
+      const uint8_t* fr = frame_ptr(a, ff[u]);
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         w[u][k] = 0u;
@@ -457,7 +457,7 @@ __global__ __launch_bounds__(kBlock) void auto_range_kernel(AutoRangeArgs a) {
   const int r0 = max(a.r_lo + 1, 0), r1 = min(a.r_hi, a.height);
   const int zw = c1 - c0, zh = r1 - r0;
   const int64_t zn = zw > 0 && zh > 0 ? (int64_t)zw * zh : 0;
-  const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* fr = frame_ptr(a, f);
   // the zone in scan order, thread tid taking pixels tid, tid + block, ...:
   // (row, col) advanced incrementally (no division per pixel)
   auto zone = [&](auto fn) {
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(kRangeBlock) void auto_range_vec_kernel(AutoRangeAr
     best[tid] = ~0ull;
   }
   __syncthreads();
-  const uint8_t* fr = a.frames + (int64_t)f * a.frame_stride;
+  const uint8_t* fr = frame_ptr(a, f);
   const int64_t plane = (int64_t)a.height * a.line_length;
   // one batch of chunks: their words (a chunk past the zone re-reads the
   // lane's first chunk and is masked), rows and first pixel columns

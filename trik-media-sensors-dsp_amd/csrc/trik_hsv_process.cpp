@@ -17,6 +17,12 @@ struct PreviewOut {
   size_t bytes;
 };
 
+// Where the sensors' cores write the run's preview: d_preview, in the handle's
+// output geometry.
+PreviewDst preview_dst(const TrikCvHandle* h, const PreviewOut& pv) {
+  return {h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes};
+}
+
 // The frame staged as a batch of one on the handle's stream (created on first
 // use), with d_sums zeroed, d_targets allocated and d_preview large enough.
 int32_t stage_frame(TrikCvHandle* h, const void* src, size_t preview_bytes, TrikHsvFrameBatch& b) {
@@ -60,8 +66,7 @@ int32_t process_ball(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
     HIP_TRY(hipMemcpyAsync(detect, h->d_auto, sizeof detect, hipMemcpyDeviceToHost, h->stream));
   }
   if (pv.bytes) {  // the preview stream (WSEQ:316-354, 471-494)
-    r = preview_core(h, b, ia, h->d_sums, 1, h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes,
-                     h->stream);
+    r = preview_core(h, b, ia, h->d_sums, 1, preview_dst(h, pv), h->stream);
     if (r) return r;
   }
   TrikHsvTarget t;
@@ -120,7 +125,7 @@ int32_t process_line(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
   if (r) return r;
   if (pv.bytes) {  // preview: window columns only, then the overlays
     r = line_preview_core(h, b, line_alg(ia.detectValFrom, ia.detectValTo), 5, h->in_w - 5, 1, h->d_sums,
-                          h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes, h->stream);
+                          preview_dst(h, pv), h->stream);
     if (r) return r;
   }
   TrikHsvTarget t;
@@ -145,8 +150,7 @@ int32_t process_wline(TrikCvHandle* h, const TrikHsvFrameBatch& b, const Preview
   r = enqueue_auto_detect(h, b, TRIK_HSV_AUTO_WEBCAM_LINE, ia.autoDetectHsv, ad);
   if (r) return r;
   if (pv.bytes) {  // every pixel (LSEQW:232-269), then the thin and target lines
-    r = line_preview_core(h, b, wr, 0, 0x7FFFFFFF, 0, h->d_sums, h->out_w, h->out_h, h->out_ll, h->d_preview,
-                          (int64_t)pv.bytes, h->stream);
+    r = line_preview_core(h, b, wr, 0, 0x7FFFFFFF, 0, h->d_sums, preview_dst(h, pv), h->stream);
     if (r) return r;
   }
   TrikHsvTarget t;
@@ -168,8 +172,7 @@ int32_t process_blob(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
   r = enqueue_auto_detect(h, b, TRIK_HSV_AUTO_OV7670_OBJECT, ia.autoDetectHsv, ad);
   if (r) return r;
   if (pv.bytes) {  // preview: set metapixels, guide lines, target marks
-    r = blob_preview_core(h, b, ba.meta, ba.top, h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes,
-                          h->stream);
+    r = blob_preview_core(h, b, ba.meta, ba.top, preview_dst(h, pv), h->stream);
     if (r) return r;
   }
   TrikHsvTarget t[8];
@@ -193,8 +196,7 @@ int32_t process_mxn(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewOu
   int32_t r = mxn_core(h, b, rows_m, cols_n, h->d_mxn_colors, nullptr, h->stream);
   if (r) return r;
   if (pv.bytes) {  // preview: every pixel, then the cells' squares
-    r = mxn_preview_core(h, b, rows_m, cols_n, h->d_mxn_colors, h->out_w, h->out_h, h->out_ll, h->d_preview,
-                         (int64_t)pv.bytes, h->stream);
+    r = mxn_preview_core(h, b, rows_m, cols_n, h->d_mxn_colors, preview_dst(h, pv), h->stream);
     if (r) return r;
   }
   int32_t colors[100];
@@ -214,8 +216,7 @@ int32_t process_edge(TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewO
   HIP_TRY(launch_edge(edge_args(b, kThreshold, h->d_sums, h->d_targets, nullptr), h->stream));
   int32_t r = 0;
   if (pv.bytes) {
-    r = edge_preview_core(h, b, kThreshold, h->d_sums, h->out_w, h->out_h, h->out_ll, h->d_preview, (int64_t)pv.bytes,
-                          h->stream);
+    r = edge_preview_core(h, b, kThreshold, h->d_sums, preview_dst(h, pv), h->stream);
     if (r) return r;
   }
   TrikHsvTarget t;

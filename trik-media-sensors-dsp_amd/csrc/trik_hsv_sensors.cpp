@@ -100,28 +100,26 @@ int32_t ensure_maps(TrikCvHandle* h, int w, int hgt, int ow, int oh, hipStream_t
   return 0;
 }
 
+// Where the previews go, with the handle's current maps (ensure_maps) for
+// frames of w x hgt: wi2wo[w], hi2ho[hgt], last_row[out_h], last_col[out_w].
+PreviewTarget preview_target(const TrikCvHandle* h, int w, int hgt, const PreviewDst& d) {
+  PreviewTarget t = {d.out_w, d.out_h, d.out_ll, d.previews, d.stride};
+  t.wi2wo = h->d_maps;
+  t.hi2ho = t.wi2wo + w;
+  t.last_row = reinterpret_cast<const int32_t*>(t.hi2ho + hgt);
+  t.last_col = t.last_row + d.out_h;
+  return t;
+}
+
 // The preview kernels' arguments on the handle's current maps.  The range is
 // the all-zero one (the multi-blob preview detects by metapixel);
 // preview_tables sets it wherever a range applies.
-PreviewArgs preview_args(const TrikCvHandle* h, const TrikHsvFrameBatch& b, int ow, int oh, int oll,
-                         uint8_t* previews, int64_t stride) {
-  PreviewArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length; a.layout = b.layout;
-  a.range = PackedRange{0, 0, 0};
-  a.aligned4 = aligned4(b) && (reinterpret_cast<uintptr_t>(previews) & 3) == 0 &&
-               (b.n_frames <= 1 || (stride & 3) == 0) && (oll & 3) == 0;
-  a.out_w = ow; a.out_h = oh; a.out_ll = oll;
-  a.previews = previews;
-  a.preview_stride = stride;
-  a.wi2wo = h->d_maps;
-  a.hi2ho = a.wi2wo + b.width;
-  a.last_row = reinterpret_cast<const int32_t*>(a.hi2ho + b.height);
-  a.last_col = a.last_row + oh;
+PreviewArgs preview_args(const TrikCvHandle* h, const TrikHsvFrameBatch& b, const PreviewDst& d) {
+  PreviewArgs a = {frame_view(b), preview_target(h, b.width, b.height, d)};
+  a.aligned4 = aligned4(b) && (reinterpret_cast<uintptr_t>(d.previews) & 3) == 0 &&
+               (b.n_frames <= 1 || (d.stride & 3) == 0) && (d.out_ll & 3) == 0;
   a.rows2_first = h->maps_rows2;
-  if (h->maps_guides) a.guide_bits = reinterpret_cast<const uint8_t*>(h->d_maps + b.width + b.height + ow + oh);
+  if (h->maps_guides) a.guide_bits = reinterpret_cast<const uint8_t*>(a.last_col + d.out_w);
   a.rows2_c0 = h->maps_rows2_c0;
   a.rows2_c1 = h->maps_rows2_c1;
   a.ovl_ok = h->maps_ovl_ok;
@@ -184,11 +182,7 @@ TRIK_VIDTRANSCODE_CV_InArgsAlg trik_hsv::line_alg(int val_from, int val_to) {
 
 LineArgs trik_hsv::line_args(const TrikHsvFrameBatch& b, int val_from, int val_to, int band_start, int band_stop,
                              TrikHsvTargetSums* sums, TrikHsvTarget* targets) {
-  LineArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  LineArgs a = {frame_view(b)};
   a.val_lo = scale_val(val_from);
   a.val_hi = scale_val(val_to);
   a.band_start = band_start;
@@ -211,11 +205,7 @@ TRIK_VIDTRANSCODE_CV_InArgsAlg trik_hsv::blob_range_args(const TRIK_VIDTRANSCODE
 }
 
 AutoRangeArgs trik_hsv::auto_range_args(const TrikHsvFrameBatch& b, uint16_t* out) {
-  AutoRangeArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length; a.layout = b.layout;
+  AutoRangeArgs a = {frame_view(b)};
   auto_range_zone(b.width, b.height, a.c_lo, a.c_hi, a.r_lo, a.r_hi);
   a.aligned4 = aligned4(b);
   a.out = out;
@@ -224,11 +214,7 @@ AutoRangeArgs trik_hsv::auto_range_args(const TrikHsvFrameBatch& b, uint16_t* ou
 
 AutoExactArgs trik_hsv::auto_exact_args(const TrikHsvFrameBatch& b, int kind, int32_t* scores, int32_t* start,
                                         uint16_t* out, int32_t* best) {
-  AutoExactArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length; a.layout = b.layout;
+  AutoExactArgs a = {frame_view(b)};
   a.kind = kind;
   auto_exact_zone(a);
   a.scores = scores; a.start = start; a.out = out; a.best = best;
@@ -276,10 +262,7 @@ int32_t blob_args(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRA
                   hipStream_t s, BlobArgs& a, TableSet** set) {
   int32_t rc = acquire_tables(h, &range, 1, s, set);
   if (rc) return rc;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  a = {frame_view(b)};
   a.range = pack_range(range);
   a.tables = (*set)->d_stripe;
   a.aligned4 = aligned4(b);
@@ -335,11 +318,10 @@ int32_t run_blob(TrikCvHandle* h, BlobArgs& ba, TableSet& t, hipStream_t s) {
 // the preview kernel writes every byte of each preview, zeros included (WFXNS:234)
 int32_t trik_hsv::preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
                                const TRIK_VIDTRANSCODE_CV_InArgsAlg& range, const TrikHsvTargetSums* sums,
-                               int sums_pitch, int ow, int oh, int oll, uint8_t* previews, int64_t stride,
-                               hipStream_t s) {
-  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+                               int sums_pitch, const PreviewDst& d, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s);
   if (rc) return rc;
-  PreviewArgs pa = preview_args(h, b, ow, oh, oll, previews, stride);
+  PreviewArgs pa = preview_args(h, b, d);
   TableSet* set = nullptr;
   rc = preview_tables(h, pa, range, s, &set);
   if (rc) return rc;
@@ -349,11 +331,10 @@ int32_t trik_hsv::preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
 
 int32_t trik_hsv::line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
                                     const TRIK_VIDTRANSCODE_CV_InArgsAlg& table_range, int col_lo, int col_hi,
-                                    int band, const TrikHsvTargetSums* sums, int ow, int oh, int oll,
-                                    uint8_t* previews, int64_t stride, hipStream_t s) {
-  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s, col_lo, col_hi);
+                                    int band, const TrikHsvTargetSums* sums, const PreviewDst& d, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s, col_lo, col_hi);
   if (rc) return rc;
-  PreviewArgs pa = preview_args(h, b, ow, oh, oll, previews, stride);
+  PreviewArgs pa = preview_args(h, b, d);
   TableSet* set = nullptr;
   rc = preview_tables(h, pa, table_range, s, &set);
   if (rc) return rc;
@@ -400,11 +381,7 @@ int32_t trik_hsv::blob_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
   for (int f0 = 0; f0 < b.n_frames && !r; f0 += chunk_frames) {
     const int nf = b.n_frames - f0 < chunk_frames ? b.n_frames - f0 : chunk_frames;
     const int64_t s0 = (int64_t)f0 * n_ranges;  // the chunk's first slot
-    BlobArgs a;
-    a.frames = static_cast<const uint8_t*>(b.frames) + (f0 ? (int64_t)f0 * b.frame_stride : 0);
-    a.frame_stride = b.frame_stride;
-    a.n_frames = nf;
-    a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+    BlobArgs a = {frame_view(b, f0, nf)};
     a.range = pack_range(ranges[0]);
     a.aligned4 = aligned4(b);
     a.meta = meta ? meta + s0 * cells : h->d_meta;
@@ -467,11 +444,7 @@ int32_t trik_hsv::mxn_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows
     }
     h->d_mxn_table = t;
   }
-  MxnArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  MxnArgs a = {frame_view(b)};
   a.rows_m = rows_m; a.cols_n = cols_n;
   a.row_step = b.height / rows_m;
   a.col_step = b.width / cols_n;
@@ -484,26 +457,14 @@ int32_t trik_hsv::mxn_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows
 }
 
 int32_t trik_hsv::mxn_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int rows_m, int cols_n,
-                                   const int32_t* colors, int ow, int oh, int oll, uint8_t* previews,
-                                   int64_t stride, hipStream_t s) {
-  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+                                   const int32_t* colors, const PreviewDst& d, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s);
   if (rc) return rc;
-  MxnPreviewArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
+  MxnPreviewArgs a = {frame_view(b), preview_target(h, b.width, b.height, d)};
   a.rows_m = rows_m; a.cols_n = cols_n;
   a.row_step = b.height / rows_m;
   a.col_step = b.width / cols_n;
   a.colors = colors;
-  a.out_w = ow; a.out_h = oh; a.out_ll = oll;
-  a.previews = previews;
-  a.preview_stride = stride;
-  a.wi2wo = h->d_maps;
-  a.hi2ho = a.wi2wo + b.width;
-  a.last_row = reinterpret_cast<const int32_t*>(a.hi2ho + b.height);
-  a.last_col = a.last_row + oh;
   HIP_TRY(launch_mxn_preview(a, s));
   return note_uses(h, nullptr, true, s);
 }
@@ -518,11 +479,7 @@ std::string trik_hsv::edge_geometry_error(int64_t width, int64_t height, int64_t
 
 EdgeArgs trik_hsv::edge_args(const TrikHsvFrameBatch& b, int threshold, TrikHsvTargetSums* sums,
                              TrikHsvTarget* targets, uint8_t* edges) {
-  EdgeArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height;
+  EdgeArgs a = {frame_view(b)};
   a.threshold = threshold;
   a.sums = sums;
   a.targets = targets;
@@ -531,24 +488,12 @@ EdgeArgs trik_hsv::edge_args(const TrikHsvFrameBatch& b, int threshold, TrikHsvT
 }
 
 int32_t trik_hsv::edge_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int threshold,
-                                    const TrikHsvTargetSums* sums, int ow, int oh, int oll, uint8_t* previews,
-                                    int64_t stride, hipStream_t s) {
-  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+                                    const TrikHsvTargetSums* sums, const PreviewDst& d, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s);
   if (rc) return rc;
-  EdgePreviewArgs a;
-  a.frames = static_cast<const uint8_t*>(b.frames);
-  a.frame_stride = b.frame_stride;
-  a.n_frames = b.n_frames;
-  a.width = b.width; a.height = b.height;
+  EdgePreviewArgs a = {frame_view(b), preview_target(h, b.width, b.height, d)};
   a.threshold = threshold;
   a.sums = sums;
-  a.out_w = ow; a.out_h = oh; a.out_ll = oll;
-  a.previews = previews;
-  a.preview_stride = stride;
-  a.wi2wo = h->d_maps;
-  a.hi2ho = a.wi2wo + b.width;
-  a.last_row = reinterpret_cast<const int32_t*>(a.hi2ho + b.height);
-  a.last_col = a.last_row + oh;
   HIP_TRY(launch_edge_preview(a, s));
   return note_uses(h, nullptr, true, s);
 }
@@ -634,28 +579,26 @@ int32_t trik_hsv::jpeg_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int qua
   JpegHeader hd;
   jpeg_divisors(quality, dv);
   jpeg_header(quality, bw, b.width, b.height, hd);
-  JpegArgs a;
-  a.frame_stride = b.frame_stride;
-  a.width = b.width; a.height = b.height; a.line_length = b.line_length;
-  a.aligned4 = aligned4(b);
-  a.ncomp = ncomp;
-  a.blocks_w = b.width / 8;
-  a.n_du = (uint32_t)n_du;
-  a.huff = h->d_jpeg_huff;
+  JpegArgs all = {frame_view(b)};
+  all.aligned4 = aligned4(b);
+  all.ncomp = ncomp;
+  all.blocks_w = b.width / 8;
+  all.n_du = (uint32_t)n_du;
+  all.huff = h->d_jpeg_huff;
   uint8_t* base = h->d_jpeg_scratch;
-  a.coeffs = reinterpret_cast<int16_t*>(base + sc.coeffs);
-  a.info = reinterpret_cast<uint32_t*>(base + sc.info);
-  a.bitoff = reinterpret_cast<unsigned long long*>(base + sc.bitoff);
-  a.total = reinterpret_cast<unsigned long long*>(base + sc.total);
-  a.words = reinterpret_cast<uint32_t*>(base + sc.words);
-  a.words_per_frame = sc.words_per_frame;
-  a.chunk_ff = reinterpret_cast<uint32_t*>(base + sc.chunk_ff);
-  a.chunks_per_frame = sc.chunks_per_frame;
-  a.out_stride = out_stride;
-  a.out_capacity = out_capacity;
+  all.coeffs = reinterpret_cast<int16_t*>(base + sc.coeffs);
+  all.info = reinterpret_cast<uint32_t*>(base + sc.info);
+  all.bitoff = reinterpret_cast<unsigned long long*>(base + sc.bitoff);
+  all.total = reinterpret_cast<unsigned long long*>(base + sc.total);
+  all.words = reinterpret_cast<uint32_t*>(base + sc.words);
+  all.words_per_frame = sc.words_per_frame;
+  all.chunk_ff = reinterpret_cast<uint32_t*>(base + sc.chunk_ff);
+  all.chunks_per_frame = sc.chunks_per_frame;
+  all.out_stride = out_stride;
+  all.out_capacity = out_capacity;
   for (int64_t f0 = 0; f0 < b.n_frames; f0 += chunk) {
-    a.n_frames = (int32_t)(b.n_frames - f0 < chunk ? b.n_frames - f0 : chunk);
-    a.frames = static_cast<const uint8_t*>(b.frames) + f0 * b.frame_stride;
+    JpegArgs a = all;
+    a.narrow(f0, b.n_frames - f0 < chunk ? b.n_frames - f0 : chunk);
     a.out = out ? out + f0 * out_stride : nullptr;
     a.sizes = sizes + f0;
     HIP_TRY(launch_jpeg(a, dv, hd, s));
@@ -667,11 +610,10 @@ int32_t trik_hsv::jpeg_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, int qua
 }
 
 int32_t trik_hsv::blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta,
-                                    const int32_t* top, int ow, int oh, int oll, uint8_t* previews, int64_t stride,
-                                    hipStream_t s) {
-  int32_t rc = ensure_maps(h, b.width, b.height, ow, oh, s);
+                                    const int32_t* top, const PreviewDst& d, hipStream_t s) {
+  int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s);
   if (rc) return rc;
-  PreviewArgs pa = preview_args(h, b, ow, oh, oll, previews, stride);
+  PreviewArgs pa = preview_args(h, b, d);
   pa.meta = meta;
   HIP_TRY(launch_preview_body(pa, s));
   HIP_TRY(launch_blob_overlay(pa, top, s));

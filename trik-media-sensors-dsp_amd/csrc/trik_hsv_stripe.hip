@@ -171,7 +171,7 @@ void stripe_kernel(KernelArgs a, StripeGeom g) {
     const int y0 = r0 + ro;
     // steps that hold at least one valid row of this tile (uniform per block)
     const int steps = min(g.steps, (a.height - r0 + g.k - 1) / g.k);
-    const uint8_t* p = a.frames + (int64_t)f * a.frame_stride + (int64_t)y0 * a.line_length + col_bytes;
+    const uint8_t* p = frame_ptr(a, f) + (int64_t)y0 * a.line_length + col_bytes;
 
     // Byte-packed per-lane counters (range t in byte t):
     //   P_i : pixels 2i and 2i+1 of the chunk    O : odd pixels
@@ -190,14 +190,14 @@ void stripe_kernel(KernelArgs a, StripeGeom g) {
     // Software pipeline, one row ahead (8 waves per SIMD hide the rest).
     // Loads are unconditional (a row past the frame end re-reads the tile's
     // first row) so the compiler can wait with a counted vmcnt.
-    const uint8_t* pf = active ? p : a.frames + (int64_t)f * a.frame_stride;
+    const uint8_t* pf = active ? p : frame_ptr(a, f);
     const int vsteps = active ? min(steps, (a.height - y0 + g.k - 1) / g.k) : 0;  // valid steps, this lane
     // The step loop, in two forms: FULL when every lane of the block is active
     // and every row of the tile lies in the frame (the common case: no
     // per-lane validity, a uniform loop counter, loads from a uniform row base
     // plus a per-lane 32-bit offset); otherwise per-lane row validity.
     const bool full = (r0 + steps * g.k <= a.height) && (g.k * g.cpr) % 64 == 0;
-    const uint8_t* tbase = a.frames + (int64_t)f * a.frame_stride + (int64_t)r0 * a.line_length;
+    const uint8_t* tbase = frame_ptr(a, f) + (int64_t)r0 * a.line_length;
     auto run = [&](auto full_c) {
       constexpr bool FULL = decltype(full_c)::value;
       // 4 pixels (words w0, w1) of row y0 + s*k at chunk pixel offset 4*half

@@ -72,6 +72,35 @@ def _batch(frames, width, height, line_length, layout, n_frames=None, frame_stri
                            layout)
 
 
+def _ptr(t) -> C.c_void_p:
+    """The tensor's device pointer, or NULL for None."""
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _preview_out(b, frames, out_width, out_height, out_line_length):
+    """A preview call's output: (out_width, out_height, out_line_length) with
+    their defaults (half the frame, two bytes per pixel) and the previews
+    tensor uint8 [N, out_height, out_line_length]; its stride is oh * oll."""
+    import torch
+
+    ow = b.width // 2 if out_width is None else out_width
+    oh = b.height // 2 if out_height is None else out_height
+    oll = 2 * ow if out_line_length is None else out_line_length
+    return ow, oh, oll, torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+
+
+def _blob_out(frames, lead, width, height, meta, labels):
+    """The multi-blob calls' output dict; `lead` = the leading axes, (N,) or (N, T)."""
+    import torch
+
+    def new(shape, dtype):
+        return torch.empty(lead + shape, dtype=dtype, device=frames.device)
+
+    cells = (height // 4, width // 4)
+    return {"targets": new((8, 4), torch.int8), "top": new((8, 3), torch.int32), "n_labels": new((), torch.int32),
+            "meta": new(cells, torch.uint8) if meta else None, "labels": new(cells, torch.int16) if labels else None}
+
+
 HOT_AUTO, HOT_STRIPE, HOT_CHROMA, HOT_GENERIC = 0, 1, 2, 3
 HOT_MIXED = 4  # last_hot_kernel(): the call's groups of 4 ranges ran different kernels
 
@@ -223,13 +252,8 @@ class Detector(_HotKernel):
                       frame_stride=None, sums_pitch=1, stream=None):
         """RGB565X previews (uint8 [N, out_height, out_line_length]) for one range;
         `sums` holds that range's per-frame sums (every `sums_pitch` entries)."""
-        import torch
-
         b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
-        ow = width // 2 if out_width is None else out_width
-        oh = height // 2 if out_height is None else out_height
-        oll = 2 * ow if out_line_length is None else out_line_length
-        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        ow, oh, oll, previews = _preview_out(b, frames, out_width, out_height, out_line_length)
         arr, _ = _ranges([hsv_range])
         rc = _lib.trik_hsv_batch_preview(self._h, C.byref(b), arr, C.c_void_p(sums.data_ptr()),
                                          sums_pitch, ow, oh, oll, C.c_void_p(previews.data_ptr()),
@@ -246,21 +270,11 @@ class Detector(_HotKernel):
         tensors: targets int8 [N, 8, 4] (x, y, size, 0), top int32 [N, 8, 3]
         (size, sum_x, sum_y), n_labels int32 [N], and meta uint8 / labels int16
         [N, H/4, W/4] when asked (else meta is the handle's scratch, None here)."""
-        import torch
-
         b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
-        dev = frames.device
-        out = {"targets": torch.empty((b.n_frames, 8, 4), dtype=torch.int8, device=dev),
-               "top": torch.empty((b.n_frames, 8, 3), dtype=torch.int32, device=dev),
-               "n_labels": torch.empty((b.n_frames,), dtype=torch.int32, device=dev),
-               "meta": torch.empty((b.n_frames, height // 4, width // 4), dtype=torch.uint8, device=dev)
-               if meta else None,
-               "labels": torch.empty((b.n_frames, height // 4, width // 4), dtype=torch.int16, device=dev)
-               if labels else None}
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        out = _blob_out(frames, (b.n_frames,), width, height, meta, labels)
         alg = _abi.OV7670InArgsAlg(1, *[int(v) for v in hsv], 0)
-        rc = _lib.trik_hsv_blob_batch(self._h, C.byref(b), C.byref(alg), ptr(out["targets"]), ptr(out["top"]),
-                                      ptr(out["meta"]), ptr(out["labels"]), ptr(out["n_labels"]),
+        rc = _lib.trik_hsv_blob_batch(self._h, C.byref(b), C.byref(alg), _ptr(out["targets"]), _ptr(out["top"]),
+                                      _ptr(out["meta"]), _ptr(out["labels"]), _ptr(out["n_labels"]),
                                       _stream_ptr(stream, frames))
         if rc:
             raise TrikHsvError(rc, "trik_hsv_blob_batch")
@@ -273,21 +287,11 @@ class Detector(_HotKernel):
         centre/tolerance range).  Returns blob_batch's dict with a range axis:
         targets int8 [N, T, 8, 4], top int32 [N, T, 8, 3], n_labels int32
         [N, T], and meta uint8 / labels int16 [N, T, H/4, W/4] when asked."""
-        import torch
-
         b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
         arr, T = _ranges(ranges)
-        dev, n = frames.device, b.n_frames
-        out = {"targets": torch.empty((n, T, 8, 4), dtype=torch.int8, device=dev),
-               "top": torch.empty((n, T, 8, 3), dtype=torch.int32, device=dev),
-               "n_labels": torch.empty((n, T), dtype=torch.int32, device=dev),
-               "meta": torch.empty((n, T, height // 4, width // 4), dtype=torch.uint8, device=dev)
-               if meta else None,
-               "labels": torch.empty((n, T, height // 4, width // 4), dtype=torch.int16, device=dev)
-               if labels else None}
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        rc = _lib.trik_hsv_blob_batch_ranges(self._h, C.byref(b), arr, T, ptr(out["targets"]), ptr(out["top"]),
-                                             ptr(out["meta"]), ptr(out["labels"]), ptr(out["n_labels"]),
+        out = _blob_out(frames, (b.n_frames, T), width, height, meta, labels)
+        rc = _lib.trik_hsv_blob_batch_ranges(self._h, C.byref(b), arr, T, _ptr(out["targets"]), _ptr(out["top"]),
+                                             _ptr(out["meta"]), _ptr(out["labels"]), _ptr(out["n_labels"]),
                                              _stream_ptr(stream, frames))
         if rc:
             raise TrikHsvError(rc, "trik_hsv_blob_batch_ranges")
@@ -296,13 +300,8 @@ class Detector(_HotKernel):
     def blob_preview(self, frames, width, height, line_length, meta, top, *, out_width=None,
                      out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
         """Multi-blob previews (uint8 [N, out_height, out_line_length]) from blob_batch's meta and top."""
-        import torch
-
         b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
-        ow = width // 2 if out_width is None else out_width
-        oh = height // 2 if out_height is None else out_height
-        oll = 2 * ow if out_line_length is None else out_line_length
-        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        ow, oh, oll, previews = _preview_out(b, frames, out_width, out_height, out_line_length)
         rc = _lib.trik_hsv_blob_preview(self._h, C.byref(b), C.c_void_p(meta.data_ptr()),
                                         C.c_void_p(top.data_ptr()), ow, oh, oll,
                                         C.c_void_p(previews.data_ptr()), oh * oll, _stream_ptr(stream, frames))
@@ -331,13 +330,8 @@ class Detector(_HotKernel):
     def mxn_preview(self, frames, width, height, line_length, m, n, colors, *, out_width=None,
                     out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
         """MxN previews (uint8 [N, out_height, out_line_length]) from mxn_batch's colors."""
-        import torch
-
         b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
-        ow = width // 2 if out_width is None else out_width
-        oh = height // 2 if out_height is None else out_height
-        oll = 2 * ow if out_line_length is None else out_line_length
-        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        ow, oh, oll, previews = _preview_out(b, frames, out_width, out_height, out_line_length)
         rc = _lib.trik_hsv_mxn_preview(self._h, C.byref(b), int(m), int(n), C.c_void_p(colors.data_ptr()),
                                        ow, oh, oll, C.c_void_p(previews.data_ptr()), oh * oll,
                                        _stream_ptr(stream, frames))
@@ -383,13 +377,8 @@ class Detector(_HotKernel):
                      frame_stride=None, stream=None):
         """Line-sensor previews (uint8 [N, out_height, out_line_length]) from the
         per-frame sums of line_batch (LSEQ:283-291, 433-467)."""
-        import torch
-
         b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
-        ow = width // 2 if out_width is None else out_width
-        oh = height // 2 if out_height is None else out_height
-        oll = 2 * ow if out_line_length is None else out_line_length
-        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        ow, oh, oll, previews = _preview_out(b, frames, out_width, out_height, out_line_length)
         rc = _lib.trik_hsv_line_preview(self._h, C.byref(b), int(val_from), int(val_to),
                                         C.c_void_p(sums.data_ptr()), ow, oh, oll,
                                         C.c_void_p(previews.data_ptr()), oh * oll, _stream_ptr(stream, frames))
@@ -402,13 +391,8 @@ class Detector(_HotKernel):
                      out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
         """Edge-line previews (uint8 [N, out_height, out_line_length], native
         uint16 RGB565 pixels) from edge_batch's sums and the same threshold."""
-        import torch
-
         b = _batch(frames, width, height, line_length, LAYOUT_OV7670, n_frames, frame_stride)
-        ow = width // 2 if out_width is None else out_width
-        oh = height // 2 if out_height is None else out_height
-        oll = 2 * ow if out_line_length is None else out_line_length
-        previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        ow, oh, oll, previews = _preview_out(b, frames, out_width, out_height, out_line_length)
         rc = _lib.trik_hsv_edge_preview(self._h, C.byref(b), int(threshold), C.c_void_p(sums.data_ptr()), ow, oh,
                                         oll, C.c_void_p(previews.data_ptr()), oh * oll,
                                         _stream_ptr(stream, frames))

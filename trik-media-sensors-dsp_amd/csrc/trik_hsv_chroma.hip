@@ -16,10 +16,11 @@
 //    stores per chroma the descriptor b1 | b2 << 8 (16 bits; 128 KB for all
 //    chromas: it lives in LDS) and per 16-chroma block the mask pair
 //    M1 | M2 << 4 (stored as its offset in a palette of <= 32 pairs).  A descriptor with b1 > b2 + 1 is a "window": the same
-//    select gives M1 below it and 0 above it, and the pixels inside it
-//    (b2 < Y < b1) are flagged for the exact path -- so a chroma of another
-//    shape costs only the pixels in its window.  The exception code
-//    kChromaExc flags both pixels of the word.
+//    select gives M1 below it and 0 above it, and a word with a pixel inside
+//    it (b2 < Y < b1) is flagged for the exact path -- so a chroma of another
+//    shape costs only the words with a pixel in its window.  The exception
+//    code kChromaExc flags every word of the chroma.  A flagged word goes to
+//    the exact path whole: the fast path counts neither of its pixels.
 //  * The hot loop per YUYV word: one v_perm for c, three LDS reads (run
 //    descriptor, block word, the byte-spread mask pair), one packed subtract
 //    of the block's cut from both Y (the stored b1, b2 are relative to it),
@@ -28,7 +29,7 @@
 //    Accumulation is the stripe kernel's (byte-packed per-lane counters,
 //    lanes own chunk columns and walk rows).
 //  * Flagged words are compacted into a per-wave LDS queue (ballot + mbcnt);
-//    every 64 queued words one "drain" round computes their flagged pixels
+//    every 64 queued words one "drain" round computes both their pixels
 //    exactly (the stripe kernel's per-pixel arithmetic, with small LDS
 //    tables: LUT43, LUT255 and the per-range H, S and V masks) and
 //    accumulates them with explicit (x, y) weights.  (Looking them up in a
@@ -145,32 +146,6 @@ __device__ __forceinline__ void st64(uint32_t a, uint32_t x, uint32_t y) {
   "v_cmp_gt_u32_sdwa %[lt1], %[d], %[t] src0_sel:BYTE_0 src1_sel:BYTE_2\n\t"                    \
   "v_cmp_ge_u32_sdwa %[le0], %[d], %[t] src0_sel:BYTE_1 src1_sel:BYTE_0\n\t"                    \
   "v_cmp_ge_u32_sdwa %[le1], %[d], %[t] src0_sel:BYTE_1 src1_sel:BYTE_2"
-// The selects; q0 / q1 per pixel (MASKS) or only their union (the word is
-// flagged: one SALU op fewer per word).
-template <bool PER_PIXEL>
-__device__ __forceinline__ void select2_impl(uint32_t w, uint32_t d, uint32_t bw, uint32_t m1, uint32_t m2, uint64_t vm,
-                                             uint32_t& e0, uint32_t& e1, uint64_t& q0, uint64_t& q1) {
-  uint64_t x, lt0, lt1, le0, le1;
-  uint32_t t;
-  asm volatile(TRIK_SELECT2_CMPS
-               : [t] "=&v"(t), [x] "=&s"(x), [lt0] "=&s"(lt0), [lt1] "=&s"(lt1), [le0] "=&s"(le0), [le1] "=&s"(le1)
-               : [w] "v"(w), [d] "v"(d), [a] "v"(bw), [k] "s"(kChromaExc));
-  if (PER_PIXEL) {
-    q0 = (x | (lt0 & ~le0)) & vm;
-    q1 = (x | (lt1 & ~le1)) & vm;
-  } else {
-    q0 = (x | (lt0 & ~le0) | (lt1 & ~le1)) & vm;
-    q1 = 0;
-  }
-  const uint64_t k0 = le0 & ~x & vm, k1 = le1 & ~x & vm;
-  asm volatile(
-      "v_cndmask_b32_e64 %[e0], %[m2], %[m1], %[lt0]\n\t"
-      "v_cndmask_b32_e64 %[e1], %[m2], %[m1], %[lt1]\n\t"
-      "v_cndmask_b32_e64 %[e0], 0, %[e0], %[k0]\n\t"
-      "v_cndmask_b32_e64 %[e1], 0, %[e1], %[k1]"
-      : [e0] "=&v"(e0), [e1] "=&v"(e1)
-      : [m1] "v"(m1), [m2] "v"(m2), [lt0] "s"(lt0), [lt1] "s"(lt1), [k0] "s"(k0), [k1] "s"(k1));
-}
 // The fast-path masks of the two pixels of YUYV word w under run descriptor
 // d = b1 | b2 << 8 (both relative to the block's cut), block word bw (cut A
 // in its byte 0) and mask pair (m1, m2): with t = (Y - A) mod 256, lt = t < b1,
@@ -178,20 +153,29 @@ __device__ __forceinline__ void select2_impl(uint32_t w, uint32_t d, uint32_t bw
 // t >= 256 - A, above every b1 and b2 of the block (<= 255 - A): neither lt
 // nor le, so it gets 0 and no flag.  Byte operands straight from t and d by
 // SDWA compares; the selects follow all compares (the VALU-writes-SGPR ->
-// v_cndmask distance needs no nops).  q0 / q1 (wave masks, SALU) flag the
-// pixels the exact path resolves: a window pixel (lt and not le, where the
-// select gives 0) or any pixel of an exception-code word (le is cleared, so
-// the select gives 0 as well).  vm masks lanes without a valid row.
-__device__ __forceinline__ void select2(uint32_t w, uint32_t d, uint32_t bw, uint32_t m1, uint32_t m2, uint64_t vm,
-                                        uint32_t& e0, uint32_t& e1, uint64_t& q0, uint64_t& q1) {
-  select2_impl<true>(w, d, bw, m1, m2, vm, e0, e1, q0, q1);
-}
-// The same, with only the word's flag (q0 | q1).
+// v_cndmask distance needs no nops).  The returned wave mask q (SALU) flags
+// the words the exact path resolves: a word with a window pixel (lt and not
+// le) or with the exception code.  A flagged word goes to the exact path
+// whole: both its pixels get 0 here (the exact mask is the truth for every
+// pixel, so the exact path need not know which pixel raised the flag).  vm
+// masks lanes without a valid row: no flag and 0 for both pixels.
 __device__ __forceinline__ uint64_t select2w(uint32_t w, uint32_t d, uint32_t bw, uint32_t m1, uint32_t m2,
                                              uint64_t vm, uint32_t& e0, uint32_t& e1) {
-  uint64_t q, unused;
-  select2_impl<false>(w, d, bw, m1, m2, vm, e0, e1, q, unused);
-  return q;
+  uint64_t x, lt0, lt1, le0, le1;
+  uint32_t t;
+  asm volatile(TRIK_SELECT2_CMPS
+               : [t] "=&v"(t), [x] "=&s"(x), [lt0] "=&s"(lt0), [lt1] "=&s"(lt1), [le0] "=&s"(le0), [le1] "=&s"(le1)
+               : [w] "v"(w), [d] "v"(d), [a] "v"(bw), [k] "s"(kChromaExc));
+  const uint64_t qw = x | (lt0 & ~le0) | (lt1 & ~le1);
+  const uint64_t k0 = le0 & ~qw & vm, k1 = le1 & ~qw & vm;
+  asm volatile(
+      "v_cndmask_b32_e64 %[e0], %[m2], %[m1], %[lt0]\n\t"
+      "v_cndmask_b32_e64 %[e1], %[m2], %[m1], %[lt1]\n\t"
+      "v_cndmask_b32_e64 %[e0], 0, %[e0], %[k0]\n\t"
+      "v_cndmask_b32_e64 %[e1], 0, %[e1], %[k1]"
+      : [e0] "=&v"(e0), [e1] "=&v"(e1)
+      : [m1] "v"(m1), [m2] "v"(m2), [lt0] "s"(lt0), [lt1] "s"(lt1), [k0] "s"(k0), [k1] "s"(k1));
+  return qw & vm;
 }
 
 // Record store (a piece's 4 words at wa, its meta word at ma) by the lanes of
@@ -228,11 +212,10 @@ __device__ __forceinline__ uint32_t shift_in(uint32_t v, uint64_t m) {
 // 4-bit mask (range t -> bit t) -> byte-spread (range t -> bit 8t)
 __device__ __forceinline__ uint32_t spread4(uint32_t m) { return (m * 0x00204081u) & 0x01010101u; }
 
-// chroma index U | V << 8 of a YUYV word (b0=Y0, b1=U, b2=Y1, b3=V)
-__device__ __forceinline__ uint32_t chroma_of(uint32_t w) { return __builtin_amdgcn_perm(w, w, 0x0C0C0301u); }
-// the same shifted left by 8 (U << 8 | V << 16): the hot loop's run-descriptor
-// address 2c is then one right shift (v_lshrrev: half the issue cost of the
-// v_lshlrev that 2c needs; C4 -1 %, scripts/ab/r05j.py)
+// chroma index U | V << 8 of a YUYV word (b0=Y0, b1=U, b2=Y1, b3=V), shifted
+// left by 8 (U << 8 | V << 16): the hot loop's run-descriptor address 2c is
+// then one right shift (v_lshrrev: half the issue cost of the v_lshlrev that
+// 2c needs; C4 -1 %, scripts/ab/r05j.py)
 __device__ __forceinline__ uint32_t chroma_of8(uint32_t w) { return __builtin_amdgcn_perm(w, w, 0x0C03010Cu); }
 
 // The exact mask (bit t = range t) of pixel PIX of YUYV word w: the stripe
@@ -873,11 +856,11 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
       }
     };
     // One drain round: lanes 0..take-1 take the last take records, resolve
-    // the first flagged word of each exactly (which of its pixels the fast
-    // path left to this path: select2; the exact masks: exact_mask) and
-    // accumulate them with explicit (x, y); a record with more flagged words
-    // goes back to the queue with its remaining bits.  Verification mode
-    // writes the exact masks.
+    // the highest-index flagged word of each exactly (both its pixels: the
+    // fast path left the word out whole, select2w; the exact masks:
+    // exact_mask) and accumulate them with explicit (x, y); a record with
+    // more flagged words goes back to the queue with its remaining bits.
+    // Verification mode writes the exact masks.
     auto drain = [&](int take) {
       resolved += (uint32_t)take;
       const uint32_t base = (uint32_t)(qn - take);
@@ -887,20 +870,14 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
       const uint32_t fl = meta & 15u;
       if (act) {
         const uint32_t i = 3u - (uint32_t)__builtin_ctz(fl);
-        const uint32_t w = *(lds32_t)(uintptr_t)(rec + 4u * i);  // the record's first flagged word
+        // the record's highest-index flagged word (bit 3 - j = word j)
+        const uint32_t w = *(lds32_t)(uintptr_t)(rec + 4u * i);
         const uint32_t x = ((meta >> 4) & 0xFFFu) * 8u + 2u * i, yr = meta >> 16;
-        const uint32_t c = chroma_of(w);
-        const uint32_t d = ld16(kLdsRuns + 2u * c), A = ld8(kLdsBlocks + 2u * (c >> 4));
-        // (as select2: the descriptor is relative to the block's cut)
-        const uint32_t lo = d & 0xFFu, hi = d >> 8, Y0 = (w - A) & 0xFFu, Y1 = ((w >> 16) - A) & 0xFFu;
-        const bool xw = d == kChromaExc;
-        const bool f0 = xw | ((Y0 < lo) & (Y0 > hi)), f1 = xw | ((Y1 < lo) & (Y1 > hi));
-        const uint32_t m0 = f0 ? exact_mask<0>(w) : 0u;
-        const uint32_t m1 = f1 ? exact_mask<1>(w) : 0u;
+        const uint32_t m0 = exact_mask<0>(w), m1 = exact_mask<1>(w);
         if (MASKS) {
           uint8_t* mp = a.masks + ((int64_t)f * a.height + r0 + yr) * a.width + x;
-          if (f0) mp[0] = a.mask_shift ? (uint8_t)(mp[0] | (m0 << a.mask_shift)) : (uint8_t)m0;
-          if (f1) mp[1] = a.mask_shift ? (uint8_t)(mp[1] | (m1 << a.mask_shift)) : (uint8_t)m1;
+          mp[0] = a.mask_shift ? (uint8_t)(mp[0] | (m0 << a.mask_shift)) : (uint8_t)m0;
+          mp[1] = a.mask_shift ? (uint8_t)(mp[1] | (m1 << a.mask_shift)) : (uint8_t)m1;
         }
         const uint32_t e0 = spread4(m0), e1 = spread4(m1);
         ex.EN += e0 + e1;
@@ -1000,13 +977,7 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
         fb_run += row_step;
 #pragma unroll
         for (int i = 0; i < CW; ++i) {
-          uint64_t q0 = 0, q1 = 0, bal;
-          if (MASKS) {
-            select2(cw[i], d[i], cut[i], mm[i].x, mm[i].y, i < 4 ? vma : vmb, e[2 * i], e[2 * i + 1], q0, q1);
-            bal = q0 | q1;
-          } else {
-            bal = select2w(cw[i], d[i], cut[i], mm[i].x, mm[i].y, i < 4 ? vma : vmb, e[2 * i], e[2 * i + 1]);
-          }
+          uint64_t bal = select2w(cw[i], d[i], cut[i], mm[i].x, mm[i].y, i < 4 ? vma : vmb, e[2 * i], e[2 * i + 1]);
           // formed here, so the word's compare masks die here (sunk into the
           // append branches they would all stay live in SGPRs)
           asm volatile("" : "+s"(bal));
@@ -1017,13 +988,15 @@ __global__ __launch_bounds__(kMaxBlock) void chroma_kernel(KernelArgs a, ChromaG
             mb |= bal;
             fb = shift_in(fb, bal);
           }
-          if (MASKS && (i < 4 ? valid : validb)) {  // verification mode: the exact path writes the flagged pixels
+          // verification mode: both pixels of an unflagged word (the exact
+          // path writes both pixels of a flagged one)
+          if (MASKS && (i < 4 ? valid : validb) && !__builtin_amdgcn_inverse_ballot_w64(bal)) {
             const int y = y0 + s * g.rstep + (i < 4 ? 0 : half);
             uint8_t* mp = a.masks + ((int64_t)f * a.height + y) * a.width + x0 + xoff(i);
             const uint8_t m0 = (uint8_t)(stripe_px::pack_bits(e[2 * i]) << a.mask_shift);
             const uint8_t m1 = (uint8_t)(stripe_px::pack_bits(e[2 * i + 1]) << a.mask_shift);
-            if (!__builtin_amdgcn_inverse_ballot_w64(q0)) mp[0] = a.mask_shift ? (uint8_t)(mp[0] | m0) : m0;
-            if (!__builtin_amdgcn_inverse_ballot_w64(q1)) mp[1] = a.mask_shift ? (uint8_t)(mp[1] | m1) : m1;
+            mp[0] = a.mask_shift ? (uint8_t)(mp[0] | m0) : m0;
+            mp[1] = a.mask_shift ? (uint8_t)(mp[1] | m1) : m1;
           }
         }
         u32x4 wa, wb;
@@ -1243,13 +1216,8 @@ __global__ __launch_bounds__(kMaxBlock) void blob_chroma_meta_kernel(BlobArgs a,
   auto drain = [&](int take) {
     if (lane < take) {
       const u32x2 ent = ld64(qbase_s + 8u * (uint32_t)lane);
-      const uint32_t w = ent.x;
-      const uint32_t c = chroma_of(w);
-      const uint32_t d = ld16(kLdsRuns + 2u * c), A = ld8(kLdsBlocks + 2u * (c >> 4));
-      const uint32_t lo = d & 0xFFu, hi = d >> 8, Y0 = (w - A) & 0xFFu, Y1 = ((w >> 16) - A) & 0xFFu;
-      const bool xw = d == kChromaExc;
-      const bool f0 = xw | ((Y0 < lo) & (Y0 > hi)), f1 = xw | ((Y1 < lo) & (Y1 > hi));
-      const uint32_t n = (f0 ? exact_mask<0>(w) & 1u : 0u) + (f1 ? exact_mask<1>(w) & 1u : 0u);
+      const uint32_t w = ent.x;  // (both pixels: the fast path left the word out whole)
+      const uint32_t n = (exact_mask<0>(w) & 1u) + (exact_mask<1>(w) & 1u);
       if (n) {
         const uint32_t owner = wave0 + (ent.y & 63u), j = ent.y >> 6;
         __hip_atomic_fetch_add((__attribute__((address_space(3))) uint32_t*)(uintptr_t)(kLdsBlobCounts + 4u * owner),
@@ -1332,10 +1300,8 @@ __global__ __launch_bounds__(kMaxBlock) void blob_chroma_meta_kernel(BlobArgs a,
         for (int i = 0; i < 4; ++i) {
           const int wi = 4 * hf + i;  // the word's index in the row: metapixel wi >> 1
           uint32_t e0, e1;
-          uint64_t q0, q1;
-          select2(w[i], d[i], cut[i], mm[i].x, mm[i].y, vm, e0, e1, q0, q1);
+          const uint64_t bal = select2w(w[i], d[i], cut[i], mm[i].x, mm[i].y, vm, e0, e1);
           cnt[wi >> 1] += e0 + e1;  // one range: the spread masks are 0 or 1
-          const uint64_t bal = q0 | q1;
           if (bal == 0) continue;  // no lane of the wave flagged this word slot (the common case)
           const uint32_t idx =
               __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));

@@ -899,6 +899,39 @@ int32_t trik_hsv_blob_batch_ranges(TRIK_VIDTRANSCODE_CV_Handle handle, const Tri
                                    TrikHsvTarget* targets_dev, int32_t* top_dev, uint8_t* meta_dev,
                                    uint16_t* labels_dev, int32_t* n_labels_dev, void* hip_stream);
 
+/* The multi-blob sensor for N frames with HSV ranges PER FRAME, read from
+ * device memory by the kernel: one camera, one calibration per frame.
+ *   ranges_dev   [n_frames][n_ranges][6] uint16 (device), the layout and the
+ *                units of trik_hsv_frame_ranges_batch (hueFrom, hueTo, satFrom,
+ *                satTo, valFrom, valTo; hue 0..359, saturation and value
+ *                0..100): a buffer written by trik_hsv_ranges_of_detect is
+ *                taken as it is.
+ * The outputs are those of trik_hsv_blob_batch_ranges, laid out by slot s =
+ * f * n_ranges + t, and slot (f, t) holds, bit for bit, what that call writes
+ * for frame f alone with the one range holding the same six numbers (targets,
+ * top, meta, labels and n_labels), on TRIK_HSV_LAYOUT_OV7670 and
+ * TRIK_HSV_LAYOUT_YUYV batches alike.  The six numbers are scaled and packed
+ * as WSEQ:425-445 does, in int32: a saturation or value above 255 -- which an
+ * InArgs byte cannot hold -- behaves as 255.
+ * No table depends on a range: H, S and V are computed per pixel, once for
+ * all n_ranges, so no table set is built or acquired.  The
+ * handle lends its scratch only; trik_hsv_set_hot_kernel does not affect the
+ * call and what trik_hsv_last_hot_kernel reports is left unchanged by it.
+ * Stream-ordered, no host synchronisation; the host never dereferences
+ * ranges_dev, the kernel reads it when it runs, so a producer earlier on the
+ * stream is seen.  The batch goes in chunks of whole frames of at most
+ * TRIK_HSV_BLOB_CHUNK_SLOTS slots, the ranges pointer advancing with each.
+ * Fails (trik_hsv_last_error()) before any GPU call and writes nothing for
+ * what trik_hsv_blob_batch_ranges refuses -- a NULL handle, batch or (N > 0)
+ * targets, an unknown layout, n_ranges outside 1..TRIK_HSV_MAX_RANGES, width
+ * % 32 or height % 4 not zero, width > 8192 or more than 30,000 labels -- and
+ * for NULL ranges_dev when N > 0.  n_frames == 0 returns 0 and touches
+ * nothing; width or height 0 zeroes targets, top and n_labels. */
+int32_t trik_hsv_blob_frame_ranges_batch(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch,
+                                         const uint16_t* ranges_dev, int32_t n_ranges,
+                                         TrikHsvTarget* targets_dev, int32_t* top_dev, uint8_t* meta_dev,
+                                         uint16_t* labels_dev, int32_t* n_labels_dev, void* hip_stream);
+
 /* The from/to range trik_hsv_blob_batch uses for a centre/tolerance range
  * (cv_bitmap_builder_reference.hpp:110-130: hue wraps in 0..359, saturation
  * and value clip to 0..100; setHsvRange is not read, autoDetectHsv of *out is

@@ -38,6 +38,13 @@
               from device memory, T = 4 and T = 1, beside trik_hsv_process_batch
               with one shared set; and at N = 256 against a loop of 256
               single-frame trik_hsv_process_batch calls with 256 range sets.
+  blob_frame_ranges (--blob-frame-ranges, a run of its own)
+              trik_hsv_blob_frame_ranges_batch: 4096 x 640x480 ov7670 scene
+              frames and their packed-YUYV twins, each frame under its own
+              ranges read from device memory, T = 1 and T = 4, beside
+              trik_hsv_blob_batch_ranges with one shared set; and at N = 256
+              against a loop of 256 single-frame trik_hsv_blob_batch_ranges
+              calls with 256 range sets.
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -74,6 +81,26 @@ def timed(fn, stream, iters):
     return a.elapsed_time(b) / iters
 
 
+def scene_frames_and_twins(F, W, H):
+    """F ov7670 scene frames (line length W) and their packed-YUYV twins (Y0 U
+    Y1 V; U = odd, V = even chroma byte), on the device."""
+    import torch
+
+    import trik_hsv
+
+    fb = 2 * H * W
+    ov = torch.empty(F * fb, dtype=torch.uint8, device="cuda")
+    trik_hsv.synth(ov, W, H, W, trik_hsv.LAYOUT_OV7670, 1, 0x7A1C)
+    yuyv = torch.empty(F * fb, dtype=torch.uint8, device="cuda")
+    for f0 in range(0, F, 256):
+        src = ov[f0 * fb:(f0 + 256) * fb].view(-1, 2, H, W)
+        dst = yuyv[f0 * fb:(f0 + 256) * fb].view(-1, H, 2 * W)
+        dst[:, :, 0::2] = src[:, 0]
+        dst[:, :, 1::4] = src[:, 1, :, 1::2]
+        dst[:, :, 3::4] = src[:, 1, :, 0::2]
+    return ov, yuyv
+
+
 def blob_ranges(args):
     """The multi-blob sensor for the four SURVEY 8(d) ranges on 640x480 scene
     frames: one trik_hsv_blob_batch_ranges call against four single-range
@@ -89,16 +116,7 @@ def blob_ranges(args):
     centres = [(15, 15, 75, 25, 65, 35), (120, 30, 70, 30, 60, 40), (230, 30, 70, 30, 60, 40),
                (355, 25, 65, 35, 65, 35)]
     assert [trik_hsv.blob_range_of(c) for c in centres] == ranges
-    fb = 2 * H * W
-    ov = torch.empty(F * fb, dtype=torch.uint8, device="cuda")
-    trik_hsv.synth(ov, W, H, W, trik_hsv.LAYOUT_OV7670, 1, 0x7A1C)
-    yuyv = torch.empty(F * fb, dtype=torch.uint8, device="cuda")  # Y0 U Y1 V; U = odd, V = even chroma byte
-    for f0 in range(0, F, 256):
-        src = ov[f0 * fb:(f0 + 256) * fb].view(-1, 2, H, W)
-        dst = yuyv[f0 * fb:(f0 + 256) * fb].view(-1, H, 2 * W)
-        dst[:, :, 0::2] = src[:, 0]
-        dst[:, :, 1::4] = src[:, 1, :, 1::2]
-        dst[:, :, 3::4] = src[:, 1, :, 0::2]
+    ov, yuyv = scene_frames_and_twins(F, W, H)
     stream = torch.cuda.current_stream()
     det = trik_hsv.Detector()
 
@@ -212,6 +230,104 @@ def frame_ranges(args):
                 "alternating rounds, all in one process"}}
 
 
+def blob_frame_ranges(args):
+    """trik_hsv_blob_frame_ranges_batch (the multi-blob sensor with HSV ranges
+    per frame, read on the device) on 640x480 ov7670 scene frames and their
+    packed-YUYV twins, alternating in this process with
+      (a) trik_hsv_blob_batch_ranges with ONE shared set at the same N and T, and
+      (b) at N = 256, a loop of 256 single-frame trik_hsv_blob_batch_ranges
+          calls with 256 different range sets (each call builds its tables) --
+          the only way to per-frame ranges without the new call.
+    Both calls run blob_ccl_kernel over the same slots; what differs is the
+    bitmap pass (a kernel trace of this mode splits the two)."""
+    import torch
+
+    import trik_hsv
+
+    W, H, F, FB = 640, 480, args.frames, 256
+    OV, YUYV = trik_hsv.LAYOUT_OV7670, trik_hsv.LAYOUT_YUYV
+    base = [(0, 30, 50, 100, 30, 100), (90, 150, 40, 100, 20, 100), (200, 260, 40, 100, 20, 100),
+            (330, 20, 30, 100, 30, 100)]  # T0-T3
+
+    def sets(n, t):  # frame f: the base ranges with every hue bound shifted by f degrees
+        return [[((hf + f) % 360, (ht + f) % 360, sf, st, vf, vt) for hf, ht, sf, st, vf, vt in base[:t]]
+                for f in range(n)]
+
+    ov, yuyv = scene_frames_and_twins(F, W, H)
+    fb = 2 * H * W
+    stream = torch.cuda.current_stream()
+    det = trik_hsv.Detector()
+    dev_sets = {t: torch.tensor(sets(F, t), dtype=torch.int16, device="cuda") for t in (4, 1)}
+    small_sets = {t: sets(FB, t) for t in (4, 1)}
+    small_dev = {t: torch.tensor(small_sets[t], dtype=torch.int16, device="cuda") for t in (4, 1)}
+    assert all(len({tuple(s) for s in small_sets[t]}) == FB for t in (4, 1))
+    frames = {"ov7670": (ov, W, OV), "yuyv": (yuyv, 2 * W, YUYV)}
+
+    def ours(lay, rng, n=None):
+        buf, ll, layout = frames[lay]
+        return lambda: det.blob_frame_ranges_batch(buf, W, H, ll, rng, layout=layout, n_frames=n, top=True)
+
+    def shared(lay, t):
+        buf, ll, layout = frames[lay]
+        return lambda: det.blob_batch_ranges(buf, W, H, ll, base[:t], layout=layout)
+
+    def loop256(t):
+        return lambda: [det.blob_batch_ranges(ov[f * fb:(f + 1) * fb], W, H, W, small_sets[t][f]) for f in range(FB)]
+
+    fns = {}
+    for lay in frames:
+        for t in (1, 4):
+            fns[f"frame_ranges_T{t}_{lay}"] = ours(lay, dev_sets[t])
+            fns[f"shared_T{t}_{lay}"] = shared(lay, t)
+    for t in (1, 4):
+        fns[f"frame_ranges_256_T{t}"] = ours("ov7670", small_dev[t], FB)
+        fns[f"loop_256_T{t}"] = loop256(t)
+    if args.only:  # a kernel trace of one pair: the timed calls of the rows whose name holds the text
+        for name in [k for k in fns if args.only in k]:
+            timed(fns[name], stream, args.iters)
+        det.close()
+        return {"blob_frame_ranges": {"only": args.only, "iters": args.iters}}
+    keys = ("targets", "top", "n_labels")
+    same = True
+    for t in (1, 4):
+        one, singles = fns[f"frame_ranges_256_T{t}"](), fns[f"loop_256_T{t}"]()
+        same = same and all(torch.equal(one[k][f], singles[f][k][0]) for k in keys for f in range(FB))
+    # frame 0's set is the shared set: its slots must agree with the shared-range call, in both layouts
+    same0 = all(torch.equal(fns[f"frame_ranges_T4_{lay}"]()[k][0], fns[f"shared_T4_{lay}"]()[k][0])
+                for k in keys for lay in frames)
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name, fn in fns.items():
+            runs[name].append(timed(fn, stream, 2 if name.startswith("loop_256") else args.iters))
+    det.close()
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name):
+        n = FB if "256" in name else F
+        t = 4 if "T4" in name else 1
+        return {"frames": n, "ranges": t, "ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]],
+                "Mslots_per_s": round(n * t / med[name] / 1e3, 3),
+                "achieved_GBs": round(n * fb / (med[name] / 1e3) / 1e9, 1)}
+
+    out = {k: row(k) for k in fns}
+    for lay in frames:
+        for t in (1, 4):
+            out[f"frame_ranges_T{t}_{lay}"]["over_shared"] = round(
+                med[f"frame_ranges_T{t}_{lay}"] / med[f"shared_T{t}_{lay}"], 3)
+    for t in (1, 4):
+        out[f"frame_ranges_256_T{t}"]["over_loop"] = round(med[f"frame_ranges_256_T{t}"] / med[f"loop_256_T{t}"], 4)
+        out[f"loop_256_T{t}"]["ms_per_call"] = round(med[f"loop_256_T{t}"] / FB, 4)
+    return {"blob_frame_ranges": {
+        "geometry": [W, H], "scene_frames": True, "iters": args.iters, "rounds": args.rounds,
+        "results_identical_256": bool(same), "frame0_equals_shared": bool(same0), **out,
+        "note": "frame_ranges_*: blob_meta_frame_ranges_kernel (exact per-pixel HSV once per pixel, ranges read from "
+                "device memory, frame f under the base ranges shifted by f degrees of hue) + blob_ccl_kernel per "
+                "chunk of 4096 slots; shared_*: trik_hsv_blob_batch_ranges, one set for the batch (warm tables; "
+                "blob_meta_ranges_kernel + blob_ccl_kernel); loop_256_*: 256 single-frame "
+                "trik_hsv_blob_batch_ranges calls, 256 different sets (2 timed iterations per round); achieved_GBs "
+                "counts the frames once (2 B/px); medians of alternating rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -225,7 +341,16 @@ def main():
     ap.add_argument("--frame-ranges", action="store_true",
                     help="the frame_ranges mode alone: per-frame ranges against the shared-range step and against a "
                          "loop of single-frame calls")
+    ap.add_argument("--blob-frame-ranges", action="store_true",
+                    help="the blob_frame_ranges mode alone: the multi-blob sensor with per-frame ranges against the "
+                         "shared-range call and against a loop of single-frame calls")
+    ap.add_argument("--only", default="",
+                    help="with --blob-frame-ranges: run only the rows whose name holds this text, once, for a kernel "
+                         "trace (e.g. T4_ov7670: the per-frame and the shared call at T = 4 on ov7670 frames)")
     args = ap.parse_args()
+    if args.blob_frame_ranges:
+        print(json.dumps(blob_frame_ranges(args)))
+        return
     if args.blob_ranges:
         print(json.dumps(blob_ranges(args)))
         return

@@ -382,6 +382,30 @@ extern "C" int32_t trik_hsv_blob_batch_ranges(TRIK_VIDTRANSCODE_CV_Handle h, con
   return blob_ranges_core(h, *b, ranges, n, targets, top, meta, labels, n_labels, s);
 }
 
+extern "C" int32_t trik_hsv_blob_frame_ranges_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                                    const uint16_t* ranges, int32_t n, TrikHsvTarget* targets,
+                                                    int32_t* top, uint8_t* meta, uint16_t* labels,
+                                                    int32_t* n_labels, void* stream) {
+  int32_t r = check_handle_batch(h, b);  // (either layout; width % 32, height % 4)
+  if (r) return r;
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES) return fail(TRIK_IVIDTRANSCODE_EFAIL, "n_ranges must be 1..64");
+  if (b->width > 8192 || blob_max_labels(b->width / 4, b->height / 4) > 30000)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "frame too large for the multi-blob sensor");
+  if (b->n_frames > 0 && !targets) return fail(TRIK_IVIDTRANSCODE_EFAIL, "targets is NULL");
+  if (b->n_frames > 0 && !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges is NULL");
+  if (b->n_frames == 0) return 0;  // (nothing is touched, the handle included)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lock(h->mu);
+  DeviceGuard dg(h->device);
+  r = check_device(h, b, targets);
+  if (r) return r;
+  const std::string e = device_buffer_error(ranges, h->device, "ranges");  // (its attributes: never its bytes)
+  if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+  if (b->width == 0 || b->height == 0)
+    return zero_blob_outputs(targets, top, n_labels, (size_t)b->n_frames * (size_t)n, s);
+  return blob_frame_ranges_core(h, *b, ranges, n, targets, top, meta, labels, n_labels, s);
+}
+
 // BMB:110-130 on the host: the centre/tolerance range in the from/to form
 extern "C" int32_t trik_hsv_blob_range_of(const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg* hsv,
                                           TRIK_VIDTRANSCODE_CV_InArgsAlg* out) {

@@ -676,7 +676,8 @@ int launch_blob(const BlobArgs& a, hipStream_t s) {
   // zeroed when it is allocated (ensure_blob_scratch) and every clusterer
   // launch zeroes the labels it used before it ends
   const int64_t total = (int64_t)a.n_frames * bw * bh;
-  if (total >= (1ll << 31) || !a.tables) return hipErrorInvalidValue;
+  // (the clusterer reads no table: over ready bitmaps a.tables may be NULL)
+  if (total >= (1ll << 31) || (!a.tables && !a.meta_ready)) return hipErrorInvalidValue;
   {
     hipError_t e = set_dynamic_lds(reinterpret_cast<const void*>(blob_meta_kernel), (int)sizeof(StripeTables));
     if (e != hipSuccess) return e;

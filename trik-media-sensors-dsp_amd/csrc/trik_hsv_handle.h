@@ -420,6 +420,11 @@ int32_t blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRA
 int32_t blob_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg* ranges,
                          int n_ranges, TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels,
                          int32_t* n_labels, hipStream_t s);
+// the same with the ranges per frame, in device memory [n_frames][n_ranges][6]
+// (no table set; the hot-kernel report is left as it is)
+int32_t blob_frame_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint16_t* ranges, int n_ranges,
+                               TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels,
+                               int32_t* n_labels, hipStream_t s);
 // its preview: set metapixels, guide lines, target marks
 int32_t blob_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint8_t* meta, const int32_t* top,
                           const PreviewDst& d, hipStream_t s);

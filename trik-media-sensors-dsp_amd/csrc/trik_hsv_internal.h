@@ -451,7 +451,8 @@ struct BlobArgs : FrameView {
   int32_t* top;              // [n][8][3]: size, sum_x, sum_y of the 8 largest clusters
   int32_t* n_labels;         // optional [n]
   int32_t meta_lds = 0;      // set by launch_blob: the bitmap staged in LDS
-  int32_t meta_ready = 0;    // the bitmap is already written (launch_blob_meta_chroma)
+  int32_t meta_ready = 0;    // the bitmap is already written (launch_blob_meta_chroma, _ranges,
+                             // _frame_ranges): launch_blob runs the clusterer alone and reads no table
   // set by launch_blob: the own statistics as one packed u64 per label,
   // size | sum_x << pack_sx | sum_y << pack_sy (0: three int32 per label)
   int32_t pack_sx = 0, pack_sy = 0;
@@ -478,6 +479,11 @@ int launch_blob_meta_chroma(const BlobArgs& a, const ChromaTables* ct, const Ran
 // a.meta + (f * n_ranges + range0 + k) * bw * bh.  launch_blob with meta_ready
 // set and n_frames = the slot count then runs the clusterer over the slots.
 int launch_blob_meta_ranges(const BlobArgs& a, int layout, int n_ranges, int range0, int live, hipStream_t s);
+// The same bitmaps with the ranges PER FRAME, read on the device
+// (trik_hsv_blob_frame_ranges.hip; no table): ranges[f][t][6] in InArgs units
+// gives a.meta + (f * n_ranges + t) * bw * bh for a.n_frames frames of
+// a.layout, all n_ranges from one read of the frames.  a.tables is not read.
+int launch_blob_meta_frame_ranges(const BlobArgs& a, const uint16_t* ranges, int n_ranges, hipStream_t s);
 // guide lines + a 3x3 mark per kept target (OSEQ:548-580), from BlobArgs.top
 int launch_blob_overlay(const PreviewArgs& a, const int32_t* top, hipStream_t s);
 

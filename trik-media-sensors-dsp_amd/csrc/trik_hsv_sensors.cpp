@@ -423,6 +423,60 @@ int32_t trik_hsv::blob_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
   return note_uses(h, set, false, s, &h->blob_users);
 }
 
+// The same with the ranges per frame, in device memory (ranges[f][t][6], never
+// read on the host): the chunks of blob_ranges_core, each one table-free bitmap
+// launch for all of its ranges, then the clusterer over its slots.  No table
+// set is acquired and the hot-kernel report is left as it is; the handle lends
+// its scratch alone.
+int32_t trik_hsv::blob_frame_ranges_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint16_t* ranges,
+                                         int n_ranges, TrikHsvTarget* targets, int32_t* top, uint8_t* meta,
+                                         uint16_t* labels, int32_t* n_labels, hipStream_t s) {
+  const int chunk_frames = TRIK_HSV_BLOB_CHUNK_SLOTS / n_ranges > 1 ? TRIK_HSV_BLOB_CHUNK_SLOTS / n_ranges : 1;
+  const int first = b.n_frames < chunk_frames ? b.n_frames : chunk_frames;
+  int32_t r = ensure_blob_scratch(h, first * n_ranges, b.width, b.height, s);
+  if (r) return r;
+  const int64_t cells = (int64_t)(b.width / 4) * (b.height / 4);
+  bool enqueued = false;
+  for (int f0 = 0; f0 < b.n_frames && !r; f0 += chunk_frames) {
+    const int nf = b.n_frames - f0 < chunk_frames ? b.n_frames - f0 : chunk_frames;
+    const int64_t s0 = (int64_t)f0 * n_ranges;  // the chunk's first slot
+    BlobArgs a = {frame_view(b, f0, nf)};
+    a.range = PackedRange{0, 0, 0};
+    a.tables = nullptr;
+    a.aligned4 = aligned4(b);
+    a.meta = meta ? meta + s0 * cells : h->d_meta;
+    a.labels = labels ? labels + s0 * cells : nullptr;
+    a.stats = h->d_blob_stats;
+    a.max_labels = (int32_t)blob_max_labels(b.width / 4, b.height / 4);
+    a.targets = targets + s0 * 8;
+    a.top = top ? top + s0 * 24 : h->d_blob_top;
+    a.n_labels = n_labels ? n_labels + s0 : nullptr;
+    int e = launch_blob_meta_frame_ranges(a, ranges + s0 * 6, n_ranges, s);  // the chunk's ranges
+    if (e != hipSuccess) {
+      r = fail(TRIK_IVIDTRANSCODE_EFAIL,
+               std::string("launch_blob_meta_frame_ranges: ") + hipGetErrorString((hipError_t)e));
+      break;
+    }
+    enqueued = true;
+    a.n_frames = nf * n_ranges;
+    a.meta_ready = 1;
+    e = launch_blob(a, s);
+    if (e != hipSuccess) {
+      h->blob_stats_dirty = true;  // (the clusterer may not have restored its statistics to zero)
+      r = fail(TRIK_IVIDTRANSCODE_EFAIL, std::string("launch_blob: ") + hipGetErrorString((hipError_t)e));
+    }
+  }
+  if (r) {  // what was enqueued still writes the scratch
+    if (enqueued) {
+      const std::string msg = last_error();
+      (void)note_uses(h, nullptr, false, s, &h->blob_users);
+      return fail(r, msg);
+    }
+    return r;
+  }
+  return note_uses(h, nullptr, false, s, &h->blob_users);
+}
+
 std::string trik_hsv::mxn_grid_error(int64_t rows_m, int64_t cols_n) {
   if (rows_m < 1 || cols_n < 1 || rows_m * cols_n > 100)
     return "the MxN sensor takes widthM >= 1, heightN >= 1 and widthM * heightN <= 100";

@@ -297,6 +297,33 @@ class Detector(_HotKernel):
             raise TrikHsvError(rc, "trik_hsv_blob_batch_ranges")
         return out
 
+    def blob_frame_ranges_batch(self, frames, width, height, line_length, ranges, *, layout=LAYOUT_OV7670,
+                                n_frames=None, frame_stride=None, top=False, meta=False, labels=False,
+                                stream=None):
+        """The multi-blob sensor over N frames of either layout with T from/to
+        ranges PER FRAME (trik_hsv_blob_frame_ranges_batch).  `ranges` is a
+        contiguous CUDA tensor [N, T, 6] of int16 / uint16 (hue_from, hue_to,
+        sat_from, sat_to, val_from, val_to), read by the kernel in stream
+        order: what ranges_of_detect writes is taken as it is.  Returns
+        blob_batch_ranges' dict, slot (f, t) being frame f under ranges[f, t]:
+        targets int8 [N, T, 8, 4], and when asked top int32 [N, T, 8, 3] with
+        n_labels int32 [N, T], meta uint8 and labels int16 [N, T, H/4, W/4]
+        (None otherwise: the call then gets NULL for them)."""
+        b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+        if (not ranges.is_cuda or ranges.dtype.itemsize != 2 or ranges.dtype.is_floating_point or ranges.dim() != 3
+                or ranges.shape[0] != b.n_frames or ranges.shape[2] != 6 or not ranges.is_contiguous()):
+            raise ValueError("ranges must be a contiguous CUDA (HIP) tensor [n_frames, T, 6] of int16 or uint16")
+        T = ranges.shape[1]
+        out = _blob_out(frames, (b.n_frames, T), width, height, meta, labels)
+        if not top:
+            out["top"] = out["n_labels"] = None
+        rc = _lib.trik_hsv_blob_frame_ranges_batch(self._h, C.byref(b), _ptr(ranges), T, _ptr(out["targets"]),
+                                                   _ptr(out["top"]), _ptr(out["meta"]), _ptr(out["labels"]),
+                                                   _ptr(out["n_labels"]), _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_blob_frame_ranges_batch")
+        return out
+
     def blob_preview(self, frames, width, height, line_length, meta, top, *, out_width=None,
                      out_height=None, out_line_length=None, n_frames=None, frame_stride=None, stream=None):
         """Multi-blob previews (uint8 [N, out_height, out_line_length]) from blob_batch's meta and top."""

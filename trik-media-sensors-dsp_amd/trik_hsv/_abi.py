@@ -249,6 +249,8 @@ PROTOTYPES = {
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
     "trik_hsv_blob_batch_ranges": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(InArgsAlg), i32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
+    "trik_hsv_blob_frame_ranges_batch": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, i32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
     "trik_hsv_blob_range_of": ([C.POINTER(OV7670InArgsAlg), C.POINTER(InArgsAlg)], i32),
     "trik_hsv_blob_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, C.c_void_p, i32, i32, i32,
                                C.c_void_p, C.c_int64, C.c_void_p], i32),

@@ -17,6 +17,7 @@ import blob_patterns
 import jpeg_cases
 import jpeg_ref
 import mxn_ref
+import preview_cases
 import ref_lib
 import test_gpu_blob as gpu_blob
 import test_gpu_line as gpu_line
@@ -130,6 +131,21 @@ def test_webcam_object_sensor_golden_cases(oracle_mod):
         _same_run(oracle_mod, fr, w, h, ll, RANGES[rname], bool(auto), ow, oh, oll, name)
         n += 1
     assert n == 1 + 4 + 4 + 12 + 12 + 5 and empty == 2
+
+
+def test_webcam_object_sensor_corner_targets(oracle_mod, table):
+    """The corner-block frames of tests/preview_cases.py (a target in each
+    corner, on each edge, in the centre, the whole frame, one pixel, 2 x 2) on
+    the 2:1, the 0.625 and the upscaled preview of the GPU tests: the target
+    circle's points are clamped to the frame and then mapped (WSEQ:72-134)."""
+    n = 0
+    for w, h, ow, oh in preview_cases.CIRCLE_GEOMS:
+        for rng in (preview_cases.T0, preview_cases.V_BAND):
+            for name in preview_cases.PLACES:
+                fr = preview_cases.corner_block(table, rng, w, h, 2 * w, LAYOUT_YUYV, name)
+                _same_run(oracle_mod, fr, w, h, 2 * w, rng, False, ow, oh, 2 * ow, ((w, h, ow, oh), rng, name))
+                n += 1
+    assert n == 3 * 2 * 12
 
 
 def test_webcam_object_sensor_rejects(oracle_mod):
@@ -384,6 +400,30 @@ def test_blob_scenes_and_dense_bitmaps(oracle_mod):
     assert n == 30 + 7 + 6 == sum(paths.values())
     print("paths", dict(paths))
     assert paths["permuted"] <= 1 and paths["cut"] <= 1  # more would widen what is accepted
+
+
+def test_ov7670_multi_blob_corner_targets(oracle_mod, table):
+    """The ov7670 counterpart of test_webcam_object_sensor_corner_targets.  The
+    reference's ov7670 object sensor is the multi-blob one: it marks its
+    targets with 3 x 3 squares and draws no circle, so the clamp-then-map
+    circle is held to the reference by the webcam test alone.  The same
+    placements as ov7670 frames, with blocks of 16 x 16 pixels (4 x 4
+    metapixels, so the corner, edge and centre blocks give kept targets),
+    through the multi-blob sensor under the same range in its centre and
+    tolerance form, on the same three previews."""
+    hsv = (15, 15, 75, 25, 65, 35)  # preview_cases.T0 as from / to: hue 0..30, sat 50..100, val 30..100
+    assert oracle_mod.blob_range(hsv) == oracle_mod.pack_range(preview_cases.T0)
+    n = marks = 0
+    for w, h, ow, oh in preview_cases.CIRCLE_GEOMS:
+        if w < 64:
+            continue  # (32 x 16 holds 8 x 4 metapixels: no room for the blocks)
+        for name in preview_cases.PLACES:
+            fr = preview_cases.corner_block(table, preview_cases.T0, w, h, w, LAYOUT_OV7670, name, size=(16, 16))
+            got, want, g = _blob_pair(oracle_mod, fr, w, h, w, hsv, out=(ow, oh, 2 * ow))
+            assert _same_blob(got, want, g, ((w, h, ow, oh), name)) == "equal"
+            marks += int(any(t[2] for t in want["targets"].tolist()))
+            n += 1
+    assert n == 2 * 12 and marks >= 2 * 9
 
 
 def test_blob_sequence_keeps_its_range(oracle_mod):

@@ -838,6 +838,52 @@ int32_t trik_hsv_line_batch(const TrikHsvFrameBatch* batch, int32_t val_from, in
                             int32_t band_start, int32_t band_stop, TrikHsvTargetSums* sums_dev,
                             TrikHsvTarget* targets_dev, void* hip_stream);
 
+/* The line sensors for N frames with a V range PER FRAME, read from device
+ * memory by the kernel: one calibration per camera or lighting condition.
+ *   ranges_dev   [n_frames][6] uint16 (device): the six-tuple layout of
+ *                trik_hsv_frame_ranges_batch and trik_hsv_ranges_of_detect
+ *                with n_ranges == 1, so one buffer serves all three calls.
+ *                Entries 4 and 5 (valFrom, valTo, percent) are read; entries
+ *                0..3 are ignored, as the reference ignores the hue and
+ *                saturation InArgs (LSEQ:392-395, LSEQW:345-348).  Each bound
+ *                is scaled on the device as LSEQ:397-398 does, in int32:
+ *                clamp(v * 255 / 100, 0, 255) (trik_hsv_line_scale_val), so a
+ *                value above 100 behaves as 255;
+ *   sums_dev     [n_frames] TrikHsvTargetSums (device), zeroed by the call;
+ *   targets_dev  [n_frames] TrikHsvTarget (device), or NULL.
+ * TRIK_HSV_LAYOUT_OV7670, the ov7670 line sensor: slot f holds exactly what
+ * trik_hsv_line_batch writes for frame f alone with (ranges[f][4],
+ * ranges[f][5]) and the same band: {points, sum_x, cross points in the sum_y
+ * slot}, window columns 5..W-5, band rows compared as uint32; targets of
+ * LSEQ:455-474.
+ * TRIK_HSV_LAYOUT_YUYV, the webcam line sensor (LSEQW:232-269, 401-417): every
+ * column and row, slot f = {points, sum_x, sum_y = sum over rows of row x the
+ * row's points}: the three numbers trik_hsv_frame_ranges_batch writes for
+ * frame f with (0, 359, 0, 100, valFrom, valTo), and the webcam line codec's
+ * process() leaves in its sums; targets with targetY 0.  band_start and
+ * band_stop are ignored.
+ * A frame whose scaled from > to detects nothing (sums 0, target 0); the
+ * other frames are unaffected.  No handle; stream-ordered, no host
+ * synchronisation; the host never dereferences ranges_dev, the kernel reads it
+ * when it runs, so a producer earlier on the stream is seen.  n_frames == 0
+ * returns 0 and touches nothing; width or height 0 zeroes sums and targets.
+ * Fails (trik_hsv_last_error()) and enqueues nothing for a NULL batch, NULL
+ * ranges or sums when n_frames > 0, an unknown layout, or a geometry the other
+ * batched calls refuse.  Input the vector kernels cannot take (a base or
+ * frame_stride not 8- / 16-byte aligned for ov7670 / YUYV, line_length no
+ * multiple of that) is read byte by byte. */
+int32_t trik_hsv_line_frame_ranges_batch(const TrikHsvFrameBatch* batch, const uint16_t* ranges_dev,
+                                         int32_t band_start, int32_t band_stop,
+                                         TrikHsvTargetSums* sums_dev, TrikHsvTarget* targets_dev,
+                                         void* hip_stream);
+
+/* The byte a line sensor compares V with for a percent bound (LSEQ:397-398):
+ * clamp(percent * 255 / 100, 0, 255) in int32, |percent| < 2^23.  The one
+ * definition trik_hsv_line_batch applies on the host and
+ * trik_hsv_line_frame_ranges_batch's kernels on the device.  Host code, no
+ * GPU call. */
+int32_t trik_hsv_line_scale_val(int32_t percent);
+
 /* The line sensor's preview for N frames (window columns, guide, band and
  * target lines, LSEQ:283-291, 433-467), from sums_dev of trik_hsv_line_batch. */
 int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch,

@@ -45,6 +45,13 @@
               trik_hsv_blob_batch_ranges with one shared set; and at N = 256
               against a loop of 256 single-frame trik_hsv_blob_batch_ranges
               calls with 256 range sets.
+  line_frame_ranges (--line-frame-ranges, a run of its own)
+              trik_hsv_line_frame_ranges_batch: 4096 x 640x480 ov7670 scene
+              frames and their packed-YUYV twins, each frame under its own V
+              range read from device memory, beside trik_hsv_line_batch with one
+              shared range, trik_hsv_frame_ranges_batch at T = 1 with hue and
+              saturation open and the shared-range object step; and at N = 256
+              against a loop of 256 single-frame trik_hsv_line_batch calls.
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -328,6 +335,98 @@ def blob_frame_ranges(args):
                 "counts the frames once (2 B/px); medians of alternating rounds, all in one process"}}
 
 
+def line_frame_ranges(args):
+    """trik_hsv_line_frame_ranges_batch (the line sensors with a V range per
+    frame, read on the device) on 640x480 scene frames and their packed-YUYV
+    twins, alternating in this process:
+      a  trik_hsv_line_batch, one shared range (0, 30) -- the unchanged path;
+      b  the new call on ov7670, every frame given that same range;
+      c  the new call on ov7670, a distinct range per frame;
+      d  the new call on the YUYV twins (the webcam line sensor);
+      e  trik_hsv_frame_ranges_batch at T = 1 with (0, 359, 0, 100, vf, vt) on
+         the same YUYV frames -- the only per-frame route before;
+      f  the shared-range object step at T = 1 on them;
+    and at N = 256: the new call against 256 single-frame trik_hsv_line_batch
+    calls with 256 different ranges.  Algorithmic bytes = the frames once
+    (2 B/px in both layouts).  --only a runs row a alone (also against another
+    build's package, TRIK_HSV_PKG_DIR)."""
+    import torch
+
+    import trik_hsv
+
+    W, H, F, FB = 640, 480, args.frames, 256
+    fb = 2 * H * W
+    ov, yuyv = scene_frames_and_twins(F, W, H)
+    stream = torch.cuda.current_stream()
+
+    def six(pairs):
+        t = torch.zeros((len(pairs), 6), dtype=torch.int16)
+        t[:, 4:] = torch.tensor(pairs, dtype=torch.int16)
+        return t.cuda()
+
+    distinct = [((7 * f) % 41, 45 + (11 * f) % 56) for f in range(F)]  # lo <= 40 < 45 <= hi
+    fns = {"a_line_batch_shared": lambda: trik_hsv.line_batch(ov, W, H, W, 0, 30)}
+    if not args.only:
+        same_dev, distinct_dev, small_dev = six([(0, 30)] * F), six(distinct), six(distinct[:FB])
+        full = torch.tensor([[(0, 359, 0, 100, lo, hi)] for lo, hi in distinct], dtype=torch.int16, device="cuda")
+        det = trik_hsv.Detector()
+        YUYV, OV = trik_hsv.LAYOUT_YUYV, trik_hsv.LAYOUT_OV7670
+
+        def loop256():
+            return [trik_hsv.line_batch(ov[f * fb:(f + 1) * fb], W, H, W, *distinct[f]) for f in range(FB)]
+
+        fns.update({
+            "b_ov7670_same_range": lambda: trik_hsv.line_frame_ranges_batch(ov, W, H, W, OV, same_dev),
+            "c_ov7670_distinct": lambda: trik_hsv.line_frame_ranges_batch(ov, W, H, W, OV, distinct_dev),
+            "d_yuyv_distinct": lambda: trik_hsv.line_frame_ranges_batch(yuyv, W, H, 2 * W, YUYV, distinct_dev),
+            "e_frame_ranges_T1_open": lambda: trik_hsv.frame_ranges_batch(yuyv, W, H, 2 * W, YUYV, full),
+            "f_shared_object_T1": lambda: det.process_batch(yuyv, W, H, 2 * W, YUYV, [(0, 359, 0, 100, 0, 30)]),
+            "line_frame_ranges_256": lambda: trik_hsv.line_frame_ranges_batch(ov, W, H, W, OV, small_dev,
+                                                                              n_frames=FB),
+            "loop_256_line_batch": loop256,
+        })
+        a, b = fns["a_line_batch_shared"](), fns["b_ov7670_same_range"]()
+        same_ab = torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+        d, e = fns["d_yuyv_distinct"](), fns["e_frame_ranges_T1_open"]()
+        same_de = torch.equal(d[0], e[0][:, 0])
+        one, singles = fns["line_frame_ranges_256"](), loop256()
+        same_256 = all(torch.equal(one[0][f], singles[f][0][0]) and torch.equal(one[1][f], singles[f][1][0])
+                       for f in range(FB))
+    # the host-bound loop first and the slow row e after it: the rows compared
+    # with each other (a, b, c, d) then follow a busy GPU, not the loop's idle one
+    order = sorted(fns, key=lambda k: (k != "loop_256_line_batch", k[0] != "e", k))
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name in order:
+            runs[name].append(timed(fns[name], stream, 2 if name == "loop_256_line_batch" else args.iters))
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name):
+        n = FB if "256" in name else F
+        nb = n * fb
+        return {"frames": n, "ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]],
+                "Mframes_per_s": round(n / med[name] / 1e3, 3), "bytes_algorithmic": nb,
+                "achieved_GBs": round(nb / (med[name] / 1e3) / 1e9, 1),
+                "hbm_frac": round(nb / (med[name] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+    out = {k: row(k) for k in fns}
+    if not args.only:
+        det.close()
+        out["b_ov7670_same_range"]["over_a"] = round(med["b_ov7670_same_range"] / med["a_line_batch_shared"], 4)
+        out["c_ov7670_distinct"]["over_a"] = round(med["c_ov7670_distinct"] / med["a_line_batch_shared"], 4)
+        out["d_yuyv_distinct"]["over_e"] = round(med["d_yuyv_distinct"] / med["e_frame_ranges_T1_open"], 4)
+        out["line_frame_ranges_256"]["over_loop"] = round(med["line_frame_ranges_256"] / med["loop_256_line_batch"], 4)
+        out["loop_256_line_batch"]["ms_per_call"] = round(med["loop_256_line_batch"] / FB, 4)
+        out.update({"b_equals_a": bool(same_ab), "d_equals_e": bool(same_de), "results_identical_256": bool(same_256)})
+    return {"line_frame_ranges": {
+        "geometry": [W, H], "scene_frames": True, "iters": args.iters, "rounds": args.rounds, **out,
+        "note": "a: memset + line_vec_kernel<ov7670, shared> + line_targets_kernel; b, c: the same with the range "
+                "read per frame by the kernel; d: line_vec_kernel<YUYV, per frame> (V-only packed 16-bit arithmetic, "
+                "sum_y by rows); e: frame_ranges_kernel (exact H, S, V per pixel); f: trik_hsv_process_batch, warm "
+                "tables; loop_256_line_batch: 256 single-frame trik_hsv_line_batch calls (2 timed iterations per "
+                "round); medians of alternating rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -347,7 +446,14 @@ def main():
     ap.add_argument("--only", default="",
                     help="with --blob-frame-ranges: run only the rows whose name holds this text, once, for a kernel "
                          "trace (e.g. T4_ov7670: the per-frame and the shared call at T = 4 on ov7670 frames)")
+    ap.add_argument("--line-frame-ranges", action="store_true",
+                    help="the line_frame_ranges mode alone: the line sensors with a V range per frame against the "
+                         "shared-range call, the object sensor's per-frame call and a loop of single-frame calls "
+                         "(--only a: the shared-range row alone)")
     args = ap.parse_args()
+    if args.line_frame_ranges:
+        print(json.dumps(line_frame_ranges(args)))
+        return
     if args.blob_frame_ranges:
         print(json.dumps(blob_frame_ranges(args)))
         return

@@ -294,6 +294,28 @@ extern "C" int32_t trik_hsv_line_batch(const TrikHsvFrameBatch* b, int32_t val_f
   return 0;
 }
 
+extern "C" int32_t trik_hsv_line_frame_ranges_batch(const TrikHsvFrameBatch* b, const uint16_t* ranges,
+                                                    int32_t band_start, int32_t band_stop, TrikHsvTargetSums* sums,
+                                                    TrikHsvTarget* targets, void* stream) {
+  const int32_t rc = check_batch(b);
+  if (rc) return rc;
+  if (b->n_frames > 0 && !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges is NULL");
+  if (b->n_frames > 0 && !sums) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (b->n_frames == 0) return 0;
+  HIP_TRY(hipMemsetAsync(sums, 0, sizeof(TrikHsvTargetSums) * (size_t)b->n_frames, s));
+  if (b->width == 0 || b->height == 0) {
+    if (targets) HIP_TRY(hipMemsetAsync(targets, 0, sizeof(TrikHsvTarget) * (size_t)b->n_frames, s));
+    return 0;
+  }
+  LineArgs a = line_args(*b, 0, 0, band_start, band_stop, sums, targets);
+  a.ranges = ranges;  // read by the kernels, never here
+  HIP_TRY(launch_line(a, s));
+  return 0;
+}
+
+extern "C" int32_t trik_hsv_line_scale_val(int32_t percent) { return (int32_t)scale_val(percent); }
+
 extern "C" int32_t trik_hsv_frame_ranges_batch(const TrikHsvFrameBatch* b, const uint16_t* ranges, int32_t n,
                                                TrikHsvTargetSums* sums, TrikHsvTarget* targets, void* stream) {
   int32_t rc = check_batch(b);

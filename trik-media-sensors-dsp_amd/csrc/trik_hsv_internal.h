@@ -355,13 +355,34 @@ __host__ __device__ inline void auto_range_scale(int kind, int h1, int h2, int s
   }
 }
 
-// ov7670 line sensor of N frames (trik_hsv_line.hip).  sums[f] = {N, sumX,
-// crossPoints} (crossPoints in the sum_y slot), zeroed by the caller.
+// A line sensor's percent V bound as the byte V is compared with (LSEQ:397-398,
+// LSEQW:350-351): pack_scale's rule in int32, so any uint16 scales without
+// overflow and everything past 255 clamps.  The one definition, for the host's
+// shared range and for the kernels that read a range per frame.
+__host__ __device__ inline uint32_t scale_val(int32_t v) { return pack_scale(v, 100); }
+
+// The V test lo <= clamp8(m >> 6) <= hi on the pre-shift int16 maximum m
+// (line_vec_kernel): mlo <= m <= mhi, tested as (u16)(m - mlo) <= kspan.  Holds
+// for lo <= hi only: an empty range is decided before (launch_line, or the
+// kernel for a range per frame).
+__host__ __device__ inline void line_window(uint32_t lo, uint32_t hi, int16_t& mlo, uint16_t& kspan) {
+  const int32_t l = lo ? 64 * (int32_t)lo : -32768, h = hi < 255u ? 64 * (int32_t)hi + 63 : 32767;
+  mlo = (int16_t)l;
+  kspan = (uint16_t)(h - l);
+}
+
+// Line sensor of N frames (trik_hsv_line.hip), zeroed sums from the caller.
+// ov7670 layout: sums[f] = {N, sumX, crossPoints} (crossPoints in the sum_y
+// slot).  YUYV layout (ranges set): the webcam line sensor's {N, sumX, sumY}
+// over every column and row, the band unused.
 struct LineArgs : FrameView {
-  uint32_t val_lo, val_hi;           // scaled V bounds (LSEQ:397-398)
+  uint32_t val_lo, val_hi;           // scaled V bounds (LSEQ:397-398), shared by the batch
   int32_t band_start, band_stop;     // cross-point rows (LSEQ:298)
   TrikHsvTargetSums* sums;
   TrikHsvTarget* targets;            // may be NULL
+  // set: frame f's bounds are ranges[6 f + 4], ranges[6 f + 5] in percent
+  // (device memory, scaled by the kernel); val_lo and val_hi are not read
+  const uint16_t* ranges = nullptr;
 };
 
 // Per-device facts, cached thread-safely per device (trik_hsv_device.cpp):

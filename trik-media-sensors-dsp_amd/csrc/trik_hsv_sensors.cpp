@@ -144,11 +144,7 @@ int32_t preview_tables(TrikCvHandle* h, PreviewArgs& pa, const TRIK_VIDTRANSCODE
 }
 
 // LSEQ:391-414: hue and saturation bounds fixed at 0..255 (unscaled), value
-// scaled as the object sensor's.
-uint32_t scale_val(int v) {
-  const int s = (v * 255) / 100;
-  return (uint32_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
-}
+// scaled as the object sensor's (scale_val, trik_hsv_internal.h).
 
 // BitmapBuilder::run's range update (cv_bitmap_builder_reference.hpp:110-130):
 // from/to around the centre (hue wraps, sat/val clip), scaled as the webcam's,

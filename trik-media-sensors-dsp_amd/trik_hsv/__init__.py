@@ -448,6 +448,52 @@ def line_batch(frames, width, height, line_length, val_from, val_to, *, band=Non
     return sums, targets
 
 
+def line_scale_val(percent: int) -> int:
+    """The byte a line sensor compares V with for a percent bound
+    (trik_hsv_line_scale_val, host code): clamp(percent * 255 / 100, 0, 255)."""
+    return int(_lib.trik_hsv_line_scale_val(int(percent)))
+
+
+def line_frame_ranges_batch(frames, width, height, line_length, layout, ranges, *, band=None, n_frames=None,
+                            frame_stride=None, targets=True, stream=None):
+    """The line sensors with a V range per frame, read on the device
+    (trik_hsv_line_frame_ranges_batch).  LAYOUT_OV7670: the ov7670 line
+    sensor, sums int64 [N, 3] = {points, sum_x, cross points} as line_batch
+    gives them frame by frame; LAYOUT_YUYV: the webcam line sensor, {points,
+    sum_x, sum_y} over every column and row (`band` unused).  `ranges` is a
+    CUDA tensor [N, 6] (or [N, 1, 6], as ranges_of_detect returns it) of int16 /
+    uint16 whose entries 4 and 5 are valFrom and valTo in percent: used as it
+    is, never copied, read by the kernel in stream order.  Or one (val_from,
+    val_to) pair for every frame, or a sequence of N pairs, expanded into such
+    a tensor on the stream.  Returns (sums, targets int8 [N, 4]); targets is
+    None with targets=False."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+    s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+    if not isinstance(ranges, torch.Tensor):
+        pairs = torch.tensor(ranges, dtype=torch.int32).reshape(-1, 2)
+        if pairs.shape[0] == 1:
+            pairs = pairs.expand(b.n_frames, 2)
+        if pairs.shape[0] != b.n_frames:
+            raise ValueError("ranges: one (val_from, val_to) pair, or one per frame")
+        host = torch.zeros((b.n_frames, 6), dtype=torch.int32)
+        host[:, 4:] = pairs
+        with torch.cuda.stream(s):
+            ranges = host.to(torch.int16).pin_memory().to(frames.device, non_blocking=True)  # (uint16 bits)
+    if (not ranges.is_cuda or ranges.dtype.itemsize != 2 or ranges.dtype.is_floating_point
+            or ranges.shape not in ((b.n_frames, 6), (b.n_frames, 1, 6)) or not ranges.is_contiguous()):
+        raise ValueError("ranges must be a contiguous CUDA (HIP) tensor [n_frames, 6] of int16 or uint16")
+    band = (height // 2, height // 2 + 80) if band is None else band
+    sums = torch.empty((b.n_frames, 3), dtype=torch.int64, device=frames.device)
+    tg = torch.empty((b.n_frames, 4), dtype=torch.int8, device=frames.device) if targets else None
+    rc = _lib.trik_hsv_line_frame_ranges_batch(C.byref(b), C.c_void_p(ranges.data_ptr()), int(band[0]), int(band[1]),
+                                               C.c_void_p(sums.data_ptr()), _ptr(tg), C.c_void_p(s.cuda_stream))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_line_frame_ranges_batch")
+    return sums, tg
+
+
 def frame_ranges_batch(frames, width, height, line_length, layout, ranges, *, n_frames=None, frame_stride=None,
                        stream=None, sums=None, targets=None):
     """The object sensor with HSV ranges per frame (trik_hsv_frame_ranges_batch):

@@ -240,6 +240,9 @@ PROTOTYPES = {
     "trik_hsv_set_auto_detect": ([C.c_void_p, i32], i32),
     "trik_hsv_line_batch": ([C.POINTER(FrameBatch), i32, i32, i32, i32, C.c_void_p, C.c_void_p,
                              C.c_void_p], i32),
+    "trik_hsv_line_frame_ranges_batch": ([C.POINTER(FrameBatch), C.c_void_p, i32, i32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p], i32),
+    "trik_hsv_line_scale_val": ([i32], i32),
     "trik_hsv_frame_ranges_batch": ([C.POINTER(FrameBatch), C.c_void_p, i32, C.c_void_p, C.c_void_p,
                                      C.c_void_p], i32),
     "trik_hsv_ranges_of_detect": ([C.c_void_p, i32, C.c_void_p, i32, i32, C.c_void_p], i32),

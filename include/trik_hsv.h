@@ -829,6 +829,45 @@ int32_t trik_hsv_frame_ranges_batch(const TrikHsvFrameBatch* batch, const uint16
 int32_t trik_hsv_ranges_of_detect(const uint16_t* detect_dev, int32_t n, uint16_t* ranges_dev, int32_t n_ranges,
                                   int32_t t, void* hip_stream);
 
+/* The object sensor's preview for N frames with an HSV range PER FRAME, read
+ * from device memory by the kernels: the operator's picture of what
+ * trik_hsv_frame_ranges_batch detected.
+ *   ranges_dev   frame f's range is the six-tuple at ranges_dev +
+ *                (f * n_ranges + t) * 6: the buffer layout and units of
+ *                trik_hsv_frame_ranges_batch, so a buffer written by
+ *                trik_hsv_ranges_of_detect or used for the sums call is taken
+ *                as it is; n_ranges is 1..TRIK_HSV_MAX_RANGES, t is
+ *                0..n_ranges-1;
+ *   sums_dev     the circle of preview f comes from sums_dev[f * sums_pitch]
+ *                (its low words, as trik_hsv_batch_preview): with the sums
+ *                call's buffer, sums_dev + t and sums_pitch = n_ranges.
+ * Preview f is, byte for byte, what trik_hsv_batch_preview writes for frame f
+ * alone with the range that holds the same six numbers and
+ * sums_dev[f * sums_pitch]: every byte of out_height x out_line_length is
+ * written, unwritten pixels and line padding as zero; the body goes through
+ * the truncated scale maps, last writer wins, detected pixels are 0x00ffff;
+ * then the eight guide lines, then the circle.  The six numbers are scaled and
+ * packed as WSEQ:425-445 does, in int32 (a saturation or value above 255
+ * behaves as 255).  Both layouts and every geometry and placement
+ * trik_hsv_batch_preview takes: padded line_length, odd frame_stride,
+ * misaligned frames and previews, any out_*.  Bytes between previews
+ * (preview_stride > out_height * out_line_length) are not touched.
+ * The handle rule is trik_hsv_batch_preview's; the handle lends its lock and
+ * its scale maps only: no table is built (H, S and V are computed per sampled
+ * pixel) and trik_hsv_last_hot_kernel's report is unchanged.
+ * Stream-ordered, with no host synchronisation but the one a change of the
+ * preview geometry costs any preview call; the host never dereferences
+ * ranges_dev or sums_dev.
+ * n_frames == 0 or no preview byte returns 0 and touches nothing; width or
+ * height 0 gives the zero fill alone.  Fails (trik_hsv_last_error()) and
+ * enqueues nothing for everything trik_hsv_batch_preview refuses, NULL
+ * ranges_dev when n_frames > 0, and n_ranges or t out of bounds. */
+int32_t trik_hsv_frame_ranges_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch,
+                                      const uint16_t* ranges_dev, int32_t n_ranges, int32_t t,
+                                      const TrikHsvTargetSums* sums_dev, int32_t sums_pitch,
+                                      int32_t out_width, int32_t out_height, int32_t out_line_length,
+                                      uint8_t* previews_dev, int64_t preview_stride, void* hip_stream);
+
 /* The line sensor for N ov7670 frames: sums_dev[i] =
  * {points, sum_x, cross points} -- cross points in the sum_y slot -- for V in
  * [val_from, val_to] (InArgs percent units) in columns 5..W-5, cross points

@@ -52,6 +52,14 @@
               shared range, trik_hsv_frame_ranges_batch at T = 1 with hue and
               saturation open and the shared-range object step; and at N = 256
               against a loop of 256 single-frame trik_hsv_line_batch calls.
+  frame_ranges_preview (--frame-ranges-preview, a run of its own)
+              trik_hsv_frame_ranges_preview: 4096 x 640x480 scene frames ->
+              320x240 previews, each frame under its own range read from device
+              memory, beside trik_hsv_batch_preview with one shared range, on
+              the YUYV frames and their ov7670 twins; a 400x300 output through
+              both gathers; at N = 256 against a loop of 256 single-frame
+              trik_hsv_batch_preview calls; and the whole device loop
+              (autoDetectHsv, ranges_of_detect, sums, preview) per step.
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -427,6 +435,112 @@ def line_frame_ranges(args):
                 "round); medians of alternating rounds, all in one process"}}
 
 
+def frame_ranges_preview(args):
+    """trik_hsv_frame_ranges_preview (the object sensor's preview with an HSV
+    range per frame, read on the device) on 640x480 scene frames -> 320x240,
+    alternating in this process:
+      a  trik_hsv_batch_preview, one shared range -- the unchanged path;
+      b  the new call, every frame given that same range (bytes compared with a);
+      c  the new call, a distinct range per frame;
+      d  (c) on the ov7670 twins of the frames;
+      e  a 400x300 output (not 2:1) through the shared-range gather and the new one;
+      f  at N = 256: the new call with 256 ranges against the loop of 256
+         single-frame trik_hsv_batch_preview calls it replaces (each builds a
+         table set);
+      g  the whole device loop per step: trik_hsv_batch_auto_range,
+         trik_hsv_ranges_of_detect, trik_hsv_frame_ranges_batch, the new call.
+    Algorithmic bytes of a preview row = the source rows the maps sample
+    (out_height rows of line_length bytes, both planes on ov7670) plus the
+    previews written; row g adds the frames read once by the sums pass."""
+    import torch
+
+    import trik_hsv
+
+    W, H, F, FB = 640, 480, args.frames, 256
+    OW, OH, GW, GH = 320, 240, 400, 300
+    YUYV, OV = trik_hsv.LAYOUT_YUYV, trik_hsv.LAYOUT_OV7670
+    T0 = (0, 30, 50, 100, 30, 100)
+    fb = 2 * H * W
+    ov, yuyv = scene_frames_and_twins(F, W, H)
+    stream = torch.cuda.current_stream()
+    det = trik_hsv.Detector()
+    distinct = [((T0[0] + f) % 360, (T0[1] + f) % 360) + T0[2:] for f in range(F)]  # T0's hue sector turned by f degrees
+    assert len(set(distinct[:FB])) == FB
+    same_dev = torch.tensor([[T0]] * F, dtype=torch.int16, device="cuda")
+    distinct_dev = torch.tensor([[r] for r in distinct], dtype=torch.int16, device="cuda")
+    small_dev = distinct_dev[:FB].contiguous()
+    sums_a, _ = det.process_batch(yuyv, W, H, 2 * W, YUYV, [T0])
+    sums_c, _ = trik_hsv.frame_ranges_batch(yuyv, W, H, 2 * W, YUYV, distinct_dev)
+    sums_small = sums_c[:FB].contiguous()
+
+    def ours(buf, ll, lay, rng, sums, ow=OW, oh=OH, n=None):
+        return lambda: det.frame_ranges_preview(buf, W, H, ll, lay, rng, sums, out_width=ow, out_height=oh, n_frames=n)
+
+    def shared(ow=OW, oh=OH):
+        return lambda: det.batch_preview(yuyv, W, H, 2 * W, YUYV, T0, sums_a, out_width=ow, out_height=oh)
+
+    def loop256():
+        return [det.batch_preview(yuyv[f * fb:(f + 1) * fb], W, H, 2 * W, YUYV, distinct[f], sums_small[f],
+                                  out_width=OW, out_height=OH) for f in range(FB)]
+
+    def device_loop():
+        d = trik_hsv.batch_auto_range(yuyv, W, H, 2 * W, YUYV)
+        r = trik_hsv.ranges_of_detect(d)
+        s, _ = trik_hsv.frame_ranges_batch(yuyv, W, H, 2 * W, YUYV, r)
+        return det.frame_ranges_preview(yuyv, W, H, 2 * W, YUYV, r, s, out_width=OW, out_height=OH)
+
+    fns = {
+        "a_batch_preview_shared": shared(),
+        "b_same_range": ours(yuyv, 2 * W, YUYV, same_dev, sums_a),
+        "c_distinct": ours(yuyv, 2 * W, YUYV, distinct_dev, sums_c),
+        "d_distinct_ov7670": ours(ov, W, OV, distinct_dev, sums_c),
+        "e_gather_shared": shared(GW, GH),
+        "e_gather_distinct": ours(yuyv, 2 * W, YUYV, distinct_dev, sums_c, GW, GH),
+        "f_256_ranges": ours(yuyv, 2 * W, YUYV, small_dev, sums_small, n=FB),
+        "f_loop_256_batch_preview": loop256,
+        "g_device_loop": device_loop,
+    }
+    same_ab = torch.equal(fns["a_batch_preview_shared"](), fns["b_same_range"]())
+    same_cd = torch.equal(fns["c_distinct"](), fns["d_distinct_ov7670"]())
+    one, singles = fns["f_256_ranges"](), loop256()
+    same_256 = all(torch.equal(one[f], singles[f][0]) for f in range(FB))
+    del one, singles
+    # the host-bound loop first: the rows compared with each other then follow a busy GPU
+    order = sorted(fns, key=lambda k: (k != "f_loop_256_batch_preview", k))
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name in order:
+            runs[name].append(timed(fns[name], stream, 2 if name == "f_loop_256_batch_preview" else args.iters))
+    det.close()
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name):
+        n = FB if "256" in name else F
+        ow, oh = (GW, GH) if name.startswith("e_") else (OW, OH)
+        nb = n * (oh * 2 * W + oh * 2 * ow) + (n * fb if name == "g_device_loop" else 0)
+        return {"frames": n, "out": [ow, oh], "ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]],
+                "Mframes_per_s": round(n / med[name] / 1e3, 3), "bytes_algorithmic": nb,
+                "achieved_GBs": round(nb / (med[name] / 1e3) / 1e9, 1),
+                "hbm_frac": round(nb / (med[name] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+    out = {k: row(k) for k in fns}
+    for k in ("b_same_range", "c_distinct", "d_distinct_ov7670"):
+        out[k]["over_a"] = round(med[k] / med["a_batch_preview_shared"], 4)
+    out["e_gather_distinct"]["over_shared"] = round(med["e_gather_distinct"] / med["e_gather_shared"], 4)
+    out["f_256_ranges"]["over_loop"] = round(med["f_256_ranges"] / med["f_loop_256_batch_preview"], 4)
+    out["f_loop_256_batch_preview"]["ms_per_call"] = round(med["f_loop_256_batch_preview"] / FB, 4)
+    return {"frame_ranges_preview": {
+        "geometry": [W, H], "scene_frames": True, "iters": args.iters, "rounds": args.rounds,
+        "b_equals_a": bool(same_ab), "d_equals_c": bool(same_cd), "results_identical_256": bool(same_256), **out,
+        "note": "a, e_gather_shared: preview_rows2_kernel / preview_gather_kernel on a warm table set + overlay_kernel; "
+                "b, c, d, f_256_ranges: fr_preview_rows2_kernel (exact H, S, V per sampled pixel, the range read per "
+                "frame by the kernel) + overlay_kernel; e_gather_distinct: fr_preview_gather_kernel; "
+                "f_loop_256_batch_preview: 256 single-frame trik_hsv_batch_preview calls with 256 ranges (2 timed "
+                "iterations per round); g: auto_range_vec_kernel, ranges_of_detect_kernel, memset + frame_ranges_kernel "
+                "+ targets_kernel, then the preview; each call allocates its previews from torch's cache; medians of "
+                "alternating rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -450,7 +564,13 @@ def main():
                     help="the line_frame_ranges mode alone: the line sensors with a V range per frame against the "
                          "shared-range call, the object sensor's per-frame call and a loop of single-frame calls "
                          "(--only a: the shared-range row alone)")
+    ap.add_argument("--frame-ranges-preview", action="store_true",
+                    help="the frame_ranges_preview mode alone: the object sensor's preview with a range per frame "
+                         "against the shared-range preview, a loop of single-frame calls and the whole device loop")
     args = ap.parse_args()
+    if args.frame_ranges_preview:
+        print(json.dumps(frame_ranges_preview(args)))
+        return
     if args.line_frame_ranges:
         print(json.dumps(line_frame_ranges(args)))
         return

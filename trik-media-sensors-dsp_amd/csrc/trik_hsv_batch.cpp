@@ -347,6 +347,30 @@ extern "C" int32_t trik_hsv_ranges_of_detect(const uint16_t* detect, int32_t n, 
   return 0;
 }
 
+extern "C" int32_t trik_hsv_frame_ranges_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                                 const uint16_t* ranges, int32_t n, int32_t t,
+                                                 const TrikHsvTargetSums* sums, int32_t sums_pitch,
+                                                 int32_t out_width, int32_t out_height, int32_t out_line_length,
+                                                 uint8_t* previews, int64_t preview_stride, void* stream) {
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
+  int32_t rc = check_handle_batch(h, b);
+  if (rc) return rc;
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES) return fail(TRIK_IVIDTRANSCODE_EFAIL, "n_ranges must be 1..64");
+  if (t < 0 || t >= n) return fail(TRIK_IVIDTRANSCODE_EFAIL, "frame_ranges_preview: t must be 0..n_ranges-1");
+  if (b->n_frames > 0 && !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges is NULL");
+  if (b->n_frames > 0 && !sums) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  rc = check_device(h, b, sums);
+  if (!rc) rc = check_preview_out(b, d, previews != nullptr, true, sums_pitch);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return locked_preview(h, b, d, [&] {
+    // (the pointer's kind is asked of the runtime; its bytes are read by the kernels alone)
+    const std::string e = device_buffer_error(ranges, h->device, "ranges");
+    if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+    return frame_ranges_preview_core(h, *b, ranges, n, t, sums, sums_pitch, d, s);
+  });
+}
+
 extern "C" int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
                                          int32_t val_from, int32_t val_to, const TrikHsvTargetSums* sums,
                                          int32_t out_width, int32_t out_height, int32_t out_line_length,

@@ -406,6 +406,11 @@ struct PreviewDst {
 // the object sensor's preview: body, guide lines and the circle from sums
 int32_t preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
                      const TrikHsvTargetSums* sums, int sums_pitch, const PreviewDst& d, hipStream_t s);
+// the same preview with frame f's range at ranges + (f * n_ranges + t) * 6 in
+// device memory (no table set; the hot-kernel report is left as it is)
+int32_t frame_ranges_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint16_t* ranges, int n_ranges,
+                                  int t, const TrikHsvTargetSums* sums, int sums_pitch, const PreviewDst& d,
+                                  hipStream_t s);
 // a line sensor's preview: source columns col_lo..col_hi write, the tables are
 // table_range's; band = 1 draws the ov7670 line sensor's band lines
 int32_t line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,

@@ -443,6 +443,19 @@ int launch_frame_ranges(const TrikHsvFrameBatch& b, const uint16_t* ranges, int 
 int launch_ranges_of_detect(const uint16_t* detect, int n, uint16_t* ranges, int n_ranges, int t, hipStream_t s);
 // preview_kernel then overlay_kernel (circle from sums[f * sums_pitch])
 int launch_preview(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
+// launch_preview's last kernel alone: overlay_kernel (the guide lines unless
+// a.guides_drawn, then the circle from sums[f * sums_pitch])
+int launch_preview_overlay(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
+// the 2:1 row kernels' conditions on maps, layout, alignment and sizes
+// (trik_hsv_operator.hip): the one predicate of launch_preview's and
+// launch_frame_ranges_preview's 2:1 forms
+bool preview_rows2_ok(const PreviewArgs& a);
+// The object sensor's preview with an HSV range PER FRAME, read on the device
+// (trik_hsv_frame_ranges_preview.hip; no table, a.tables and a.range are not
+// read): frame f under the six-tuple at ranges + (f * n_ranges + t) * 6 in
+// InArgs units, then overlay_kernel with sums[f * sums_pitch].
+int launch_frame_ranges_preview(const PreviewArgs& a, const uint16_t* ranges, int n_ranges, int t,
+                                const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
 int launch_auto_range(const AutoRangeArgs& a, hipStream_t s);
 int launch_line(const LineArgs& a, hipStream_t s);
 // preview body as launch_preview's first kernel, then the line sensor's overlay

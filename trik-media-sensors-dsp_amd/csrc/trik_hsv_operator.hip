@@ -766,32 +766,40 @@ __global__ __launch_bounds__(kRangeBlock) void auto_range_vec_kernel(AutoRangeAr
 
 }  // namespace
 
-// The 2:1 row kernel when the maps, layout and alignment allow (see
-// preview_rows2_kernel); hipErrorNotSupported otherwise.
-static int launch_rows2(const PreviewArgs& a, hipStream_t s, bool guides = false) {
+// Whether the 2:1 row kernels take this call's maps, layout, alignment and
+// sizes: preview_rows2_kernel here and the per-frame-range twin
+// (trik_hsv_frame_ranges_preview.hip) read and write the same units under the
+// same 32-bit offsets, so both launchers ask this one predicate.
+bool preview_rows2_ok(const PreviewArgs& a) {
   const bool yuyv = a.layout == TRIK_HSV_LAYOUT_YUYV;
   const int px = 8;  // output pixels per unit
-  if (a.rows2_first < 0 || (!yuyv && a.layout != TRIK_HSV_LAYOUT_OV7670) || a.out_w % px || a.out_ll != 2 * a.out_w ||
-      (!a.meta && !a.tables))
-    return hipErrorNotSupported;
+  if (a.rows2_first < 0 || (!yuyv && a.layout != TRIK_HSV_LAYOUT_OV7670) || a.out_w % px || a.out_ll != 2 * a.out_w)
+    return false;
   // every unit loads source pixels 2c .. 2c + 1 of each of its output columns
   // c < out_w, written or not (WIN masks the unwritten ones after the load):
   // they must lie in the row, or the last row of the last frame reads past
   // the buffer (e.g. a 480-wide frame under a 320-wide preview)
-  if (2LL * a.out_w > a.width) return hipErrorNotSupported;
+  if (2LL * a.out_w > a.width) return false;
   const auto al = [](int64_t v, int64_t m) { return v % m == 0; };
   if (!al((int64_t)reinterpret_cast<uintptr_t>(a.frames), 16) || !al(a.line_length, 16) ||
       (a.n_frames > 1 && !al(a.frame_stride, 16)) || !al((int64_t)reinterpret_cast<uintptr_t>(a.previews), 8) ||
       (a.n_frames > 1 && !al(a.preview_stride, 8)))
-    return hipErrorNotSupported;
+    return false;
   const int64_t gpr = a.out_w / px, total = (int64_t)a.n_frames * a.out_h * gpr;
-  if (total >= (1ll << 31)) return hipErrorNotSupported;
+  if (total >= (1ll << 31)) return false;
   // the kernel's 32-bit strides and in-frame offsets, 24-bit row indices and line lengths
   const int64_t frame_bytes = (int64_t)a.height * a.line_length * (yuyv ? 1 : 2);
-  if (a.frame_stride >= (1ll << 32) || a.preview_stride >= (1ll << 32) || frame_bytes >= (1ll << 32) ||
-      (int64_t)a.out_h * a.out_ll >= (1ll << 32) || a.line_length >= (1 << 24) || a.out_ll >= (1 << 24) ||
-      a.height >= (1 << 24))
-    return hipErrorNotSupported;
+  return !(a.frame_stride >= (1ll << 32) || a.preview_stride >= (1ll << 32) || frame_bytes >= (1ll << 32) ||
+           (int64_t)a.out_h * a.out_ll >= (1ll << 32) || a.line_length >= (1 << 24) || a.out_ll >= (1 << 24) ||
+           a.height >= (1 << 24));
+}
+
+// The 2:1 row kernel when the maps, layout and alignment allow (see
+// preview_rows2_kernel); hipErrorNotSupported otherwise.
+static int launch_rows2(const PreviewArgs& a, hipStream_t s, bool guides = false) {
+  if (!preview_rows2_ok(a) || (!a.meta && !a.tables)) return hipErrorNotSupported;
+  const bool yuyv = a.layout == TRIK_HSV_LAYOUT_YUYV;
+  const int64_t gpr = a.out_w / 8, total = (int64_t)a.n_frames * a.out_h * gpr;
   if (total == 0) return hipSuccess;
   const bool win = a.rows2_c0 > 0 || a.rows2_c1 < a.out_w, hue_free = a.hue_free && !a.meta;
   const bool ovl = a.ovl_sums != nullptr;
@@ -901,7 +909,11 @@ int launch_preview(const PreviewArgs& pa, const TrikHsvTargetSums* sums, int sum
     a.guides_drawn = e == hipSuccess ? 1 : 0;
   }
   if (e == hipErrorNotSupported) e = (hipError_t)launch_gather(a, s);
-  if (e != hipSuccess || a.width <= 0 || a.height <= 0) return e;
+  return e != hipSuccess ? e : launch_preview_overlay(a, sums, sums_pitch, s);
+}
+
+int launch_preview_overlay(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s) {
+  if (a.width <= 0 || a.height <= 0) return hipSuccess;
   const size_t map_bytes = sizeof(uint32_t) * ((size_t)a.width + (size_t)a.height);
   if (map_bytes <= kMapLdsBytes)
     hipLaunchKernelGGL(overlay_kernel<true>, dim3((unsigned)a.n_frames), dim3(64), map_bytes, s, a, sums, sums_pitch);

@@ -325,6 +325,16 @@ int32_t trik_hsv::preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
   return note_uses(h, set, true, s);
 }
 
+// the handle lends its maps only: no table set is acquired, the ranges are read by the kernels
+int32_t trik_hsv::frame_ranges_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint16_t* ranges,
+                                            int n_ranges, int t, const TrikHsvTargetSums* sums, int sums_pitch,
+                                            const PreviewDst& d, hipStream_t s) {
+  const int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s);
+  if (rc) return rc;
+  HIP_TRY(launch_frame_ranges_preview(preview_args(h, b, d), ranges, n_ranges, t, sums, sums_pitch, s));
+  return note_uses(h, nullptr, true, s);
+}
+
 int32_t trik_hsv::line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
                                     const TRIK_VIDTRANSCODE_CV_InArgsAlg& table_range, int col_lo, int col_hi,
                                     int band, const TrikHsvTargetSums* sums, const PreviewDst& d, hipStream_t s) {

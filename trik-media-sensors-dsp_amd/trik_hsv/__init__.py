@@ -262,6 +262,41 @@ class Detector(_HotKernel):
             raise TrikHsvError(rc, "trik_hsv_batch_preview")
         return previews
 
+    def frame_ranges_preview(self, frames, width, height, line_length, layout, ranges, sums, *, t=0,
+                             sums_pitch=None, out_width=None, out_height=None, out_line_length=None,
+                             n_frames=None, frame_stride=None, stream=None):
+        """RGB565X previews (uint8 [N, out_height, out_line_length]) with an HSV
+        range per frame (trik_hsv_frame_ranges_preview): frame f under
+        ranges[f, t], a CUDA tensor [N, T, 6] of int16 / uint16 as
+        frame_ranges_batch takes it, read by the kernels in stream order.  The
+        circle of preview f comes from sums[f * sums_pitch]; `sums` is the sums
+        call's tensor [N, T, 3] (entry t is taken, the pitch is T), one row
+        per frame [N, 3], or any tensor that starts at frame 0's sums, with
+        `sums_pitch` given."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+        if (not isinstance(ranges, torch.Tensor) or not ranges.is_cuda or ranges.dtype.itemsize != 2
+                or ranges.dtype.is_floating_point or ranges.dim() != 3 or ranges.shape[0] != b.n_frames
+                or ranges.shape[2] != 6 or not ranges.is_contiguous()):
+            raise ValueError("ranges must be a contiguous CUDA (HIP) tensor [n_frames, T, 6] of int16 or uint16")
+        T = ranges.shape[1]
+        sums_ptr = sums.data_ptr()
+        if sums_pitch is None and tuple(sums.shape) == (b.n_frames, 3) and sums.is_contiguous():
+            sums_pitch = 1  # one sums row per frame
+        if sums_pitch is None:
+            if sums.dim() != 3 or tuple(sums.shape) != (b.n_frames, T, 3) or not sums.is_contiguous():
+                raise ValueError("sums must be the contiguous [n_frames, T, 3] tensor of the sums call, or sums_pitch given")
+            sums_pitch = T
+            if 0 <= t < T:
+                sums_ptr += 24 * int(t)
+        ow, oh, oll, previews = _preview_out(b, frames, out_width, out_height, out_line_length)
+        rc = _lib.trik_hsv_frame_ranges_preview(self._h, C.byref(b), C.c_void_p(ranges.data_ptr()), T, int(t),
+                                                C.c_void_p(sums_ptr), sums_pitch, ow, oh, oll,
+                                                C.c_void_p(previews.data_ptr()), oh * oll, _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_frame_ranges_preview")
+        return previews
 
     def blob_batch(self, frames, width, height, line_length, hsv, *, n_frames=None, frame_stride=None,
                    meta=False, labels=False, stream=None):

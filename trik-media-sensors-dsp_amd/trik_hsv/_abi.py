@@ -246,6 +246,8 @@ PROTOTYPES = {
     "trik_hsv_frame_ranges_batch": ([C.POINTER(FrameBatch), C.c_void_p, i32, C.c_void_p, C.c_void_p,
                                      C.c_void_p], i32),
     "trik_hsv_ranges_of_detect": ([C.c_void_p, i32, C.c_void_p, i32, i32, C.c_void_p], i32),
+    "trik_hsv_frame_ranges_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, i32, i32, C.c_void_p, i32,
+                                       i32, i32, i32, C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_line_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,
                                C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_blob_batch": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(OV7670InArgsAlg), C.c_void_p,

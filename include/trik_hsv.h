@@ -930,6 +930,53 @@ int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvF
                               int32_t out_width, int32_t out_height, int32_t out_line_length,
                               uint8_t* previews_dev, int64_t preview_stride, void* hip_stream);
 
+/* The line sensors' previews for N frames with a V range PER FRAME, read from
+ * device memory by the kernels: the operator's picture of what
+ * trik_hsv_line_frame_ranges_batch detected.
+ *   ranges_dev   [n_frames][6] uint16 (device), the buffer of
+ *                trik_hsv_line_frame_ranges_batch taken as it is: entries 4 and
+ *                5 (valFrom, valTo, percent) are read, entries 0..3 ignored.
+ *                Each bound is scaled on the device as
+ *                trik_hsv_line_scale_val does, so a value above 100 behaves as
+ *                255.  A frame whose scaled from > to has no detected pixel;
+ *                its colours and overlays are drawn as usual;
+ *   sums_dev     [n_frames] TrikHsvTargetSums (device): frame f's target line
+ *                comes from sums_dev[f], the low words of points and sum_x,
+ *                drawn when points > 10 -- the numbers trik_hsv_line_preview
+ *                reads.  The buffer trik_hsv_line_frame_ranges_batch wrote is
+ *                taken as it is.
+ * TRIK_HSV_LAYOUT_OV7670, the ov7670 line sensor: preview f is, byte for byte,
+ * what trik_hsv_line_preview writes for frame f alone with (ranges[f][4],
+ * ranges[f][5]) and sums_dev[f]: only source columns 5..W-5 write, detected
+ * pixels are 0x00ffff, then the four magenta thin lines, the two red band
+ * lines at the rows of H/2 and H/2+80 and the red three-column target line,
+ * each through drawOutputPixelBound (LSEQ:283-291, 419-474).
+ * TRIK_HSV_LAYOUT_YUYV, the webcam line sensor: preview f is, byte for byte,
+ * what the webcam line codec's process() writes for that frame and range with
+ * the same output geometry (LSEQW:232-269, 396-413): every column writes, the
+ * thin lines and the target line, no band lines.
+ * Every byte of out_height x out_line_length is written, unwritten pixels and
+ * line padding as zero; bytes between previews (preview_stride > out_height *
+ * out_line_length) are not touched.  Every geometry and placement
+ * trik_hsv_batch_preview takes: padded line_length, odd frame_stride,
+ * misaligned frames and previews, any out_*.
+ * The handle rule is trik_hsv_batch_preview's and any handle serves either
+ * layout; the handle lends its lock and its scale maps only (for ov7670 the
+ * maps with the 5..W-5 column window): no table is built or looked up (V is
+ * the maximum of the colour the preview computes anyway) and
+ * trik_hsv_last_hot_kernel's report is unchanged.  Stream-ordered, with no
+ * host synchronisation but the one a change of the preview geometry costs any
+ * preview call; the host never dereferences ranges_dev or sums_dev.
+ * n_frames == 0 or no preview byte returns 0 and touches nothing; width or
+ * height 0 gives the zero fill alone.  Fails (trik_hsv_last_error()) and
+ * enqueues nothing for everything trik_hsv_batch_preview refuses, an unknown
+ * layout, NULL ranges_dev, sums_dev or previews_dev when there are frames, and
+ * a ranges_dev that is not device-accessible memory of the handle's device. */
+int32_t trik_hsv_line_frame_ranges_preview(TRIK_VIDTRANSCODE_CV_Handle handle, const TrikHsvFrameBatch* batch,
+                                           const uint16_t* ranges_dev, const TrikHsvTargetSums* sums_dev,
+                                           int32_t out_width, int32_t out_height, int32_t out_line_length,
+                                           uint8_t* previews_dev, int64_t preview_stride, void* hip_stream);
+
 /* The ov7670 multi-blob sensor for N ov7670 frames,
  * one HSV range given as the InArgs centre/tolerance (converted as
  * cv_bitmap_builder_reference.hpp:110-130):

@@ -60,6 +60,14 @@
               both gathers; at N = 256 against a loop of 256 single-frame
               trik_hsv_batch_preview calls; and the whole device loop
               (autoDetectHsv, ranges_of_detect, sums, preview) per step.
+  line_frame_ranges_preview (--line-frame-ranges-preview, a run of its own)
+              trik_hsv_line_frame_ranges_preview: 4096 x 640x480 ov7670 scene
+              frames -> 320x240 previews, each frame under its own V range read
+              from device memory, beside trik_hsv_line_preview with one shared
+              range; the same on the packed-YUYV twins (the webcam line
+              sensor); a 400x300 output through both gathers; at N = 256
+              against a loop of 256 single-frame trik_hsv_line_preview calls;
+              and the whole device loop of the ov7670 line kind per step.
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -541,6 +549,126 @@ def frame_ranges_preview(args):
                 "alternating rounds, all in one process"}}
 
 
+def line_frame_ranges_preview(args):
+    """trik_hsv_line_frame_ranges_preview (the line sensors' previews with a V
+    range per frame, read on the device) on 640x480 scene frames -> 320x240,
+    alternating in this process:
+      a  trik_hsv_line_preview, one shared range -- the unchanged path;
+      b  the new call on the ov7670 frames, every frame given that same range
+         (bytes compared with a);
+      c  the new call, a distinct V range per frame, ov7670;
+      d  (c) on the packed-YUYV twins (the webcam line sensor's preview);
+      e  a 400x300 output (not 2:1) through the shared-range gather and the new one;
+      f  at N = 256: the new call with 256 ranges against the loop of 256
+         single-frame trik_hsv_line_preview calls it replaces (each builds or
+         looks up a table set);
+      g  the whole device loop per step for the ov7670 line kind:
+         trik_hsv_batch_auto_range_exact, trik_hsv_ranges_of_detect,
+         trik_hsv_line_frame_ranges_batch, the new call.
+    The yardstick of b and c is a in the same run; the margin is the spread of
+    a's own per-round values.  Algorithmic bytes of a preview row = the source
+    rows the maps sample (out_height rows of line_length bytes, both planes on
+    ov7670) plus the previews written; row g adds the frames read once each by
+    the auto-range pass and by the sums pass."""
+    import torch
+
+    import trik_hsv
+
+    W, H, F, FB = 640, 480, args.frames, 256
+    OW, OH, GW, GH = 320, 240, 400, 300
+    YUYV, OV = trik_hsv.LAYOUT_YUYV, trik_hsv.LAYOUT_OV7670
+    SHARED = (0, 30)
+    fb = 2 * H * W
+    ov, yuyv = scene_frames_and_twins(F, W, H)
+    stream = torch.cuda.current_stream()
+    det = trik_hsv.Detector()
+    valid = [(lo, hi) for lo in range(101) for hi in range(lo, 101)]
+    distinct = [valid[(1009 * f + 17) % len(valid)] for f in range(F)]  # a stride coprime to the 5151 pairs
+    assert len(set(distinct)) == min(F, len(valid))
+
+    def six(pairs):
+        return torch.tensor([(0, 0, 0, 0) + tuple(p) for p in pairs], dtype=torch.int16, device="cuda")
+
+    same_dev, distinct_dev = six([SHARED] * F), six(distinct)
+    small_dev = distinct_dev[:FB].contiguous()
+    sums_a, _ = trik_hsv.line_batch(ov, W, H, W, *SHARED)
+    sums_c, _ = trik_hsv.line_frame_ranges_batch(ov, W, H, W, OV, distinct_dev)
+    sums_d, _ = trik_hsv.line_frame_ranges_batch(yuyv, W, H, 2 * W, YUYV, distinct_dev)
+    sums_small = sums_c[:FB].contiguous()
+
+    def ours(buf, ll, lay, rng, sums, ow=OW, oh=OH, n=None):
+        return lambda: det.line_frame_ranges_preview(buf, W, H, ll, lay, rng, sums, out_width=ow, out_height=oh,
+                                                     n_frames=n)
+
+    def shared(ow=OW, oh=OH):
+        return lambda: det.line_preview(ov, W, H, W, *SHARED, sums_a, out_width=ow, out_height=oh)
+
+    def loop256():
+        return [det.line_preview(ov[f * fb:(f + 1) * fb], W, H, W, *distinct[f], sums_small[f], out_width=OW,
+                                 out_height=OH) for f in range(FB)]
+
+    def device_loop():
+        d, _ = trik_hsv.batch_auto_range_exact(ov, W, H, W, trik_hsv.AUTO_OV7670_LINE)
+        r = trik_hsv.ranges_of_detect(d, n_ranges=1)
+        s, _ = trik_hsv.line_frame_ranges_batch(ov, W, H, W, OV, r)
+        return det.line_frame_ranges_preview(ov, W, H, W, OV, r, s, out_width=OW, out_height=OH)
+
+    fns = {
+        "a_line_preview_shared": shared(),
+        "b_same_range": ours(ov, W, OV, same_dev, sums_a),
+        "c_distinct": ours(ov, W, OV, distinct_dev, sums_c),
+        "d_distinct_yuyv": ours(yuyv, 2 * W, YUYV, distinct_dev, sums_d),
+        "e_gather_shared": shared(GW, GH),
+        "e_gather_distinct": ours(ov, W, OV, distinct_dev, sums_c, GW, GH),
+        "f_256_ranges": ours(ov, W, OV, small_dev, sums_small, n=FB),
+        "f_loop_256_line_preview": loop256,
+        "g_device_loop": device_loop,
+    }
+    same_ab = torch.equal(fns["a_line_preview_shared"](), fns["b_same_range"]())
+    one, singles = fns["f_256_ranges"](), loop256()
+    same_256 = all(torch.equal(one[f], singles[f][0]) for f in range(FB))
+    del one, singles
+    # the host-bound loop first: the rows compared with each other then follow a busy GPU
+    order = sorted(fns, key=lambda k: (k != "f_loop_256_line_preview", k))
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name in order:
+            runs[name].append(timed(fns[name], stream, 2 if name == "f_loop_256_line_preview" else args.iters))
+    det.close()
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name):
+        n = FB if "256" in name else F
+        ow, oh = (GW, GH) if name.startswith("e_") else (OW, OH)
+        nb = n * (oh * 2 * W + oh * 2 * ow) + (2 * n * fb if name == "g_device_loop" else 0)
+        return {"frames": n, "out": [ow, oh], "ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]],
+                "Mframes_per_s": round(n / med[name] / 1e3, 3), "bytes_algorithmic": nb,
+                "achieved_GBs": round(nb / (med[name] / 1e3) / 1e9, 1),
+                "hbm_frac": round(nb / (med[name] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+    out = {k: row(k) for k in fns}
+    a_runs = runs["a_line_preview_shared"]
+    spread = (max(a_runs) - min(a_runs)) / med["a_line_preview_shared"]
+    out["a_line_preview_shared"]["spread_of_rounds"] = round(spread, 4)
+    for k in ("b_same_range", "c_distinct", "d_distinct_yuyv"):
+        out[k]["over_a"] = round(med[k] / med["a_line_preview_shared"], 4)
+        out[k]["within_a_spread"] = bool(med[k] <= med["a_line_preview_shared"] * (1 + spread))
+    out["e_gather_distinct"]["over_shared"] = round(med["e_gather_distinct"] / med["e_gather_shared"], 4)
+    out["f_256_ranges"]["over_loop"] = round(med["f_256_ranges"] / med["f_loop_256_line_preview"], 4)
+    out["f_loop_256_line_preview"]["ms_per_call"] = round(med["f_loop_256_line_preview"] / FB, 4)
+    return {"line_frame_ranges_preview": {
+        "geometry": [W, H], "scene_frames": True, "iters": args.iters, "rounds": args.rounds,
+        "b_equals_a": bool(same_ab), "results_identical_256": bool(same_256), **out,
+        "note": "a, e_gather_shared: preview_rows2_kernel<WIN, HUEFREE, OVL> / preview_gather_kernel + "
+                "line_overlay_kernel on a warm table set; b, c, d, f_256_ranges: lfr_preview_rows2_kernel (V = max of "
+                "the clamped colour, the bounds and the target line read per frame by the kernel, no LDS); "
+                "e_gather_distinct: lfr_preview_gather_kernel + line_overlay_kernel; f_loop_256_line_preview: 256 "
+                "single-frame trik_hsv_line_preview calls with 256 ranges (2 timed iterations per round); g: the "
+                "exact auto-range kernels, ranges_of_detect_kernel, memset + line_vec_kernel + line_targets_kernel, "
+                "then the preview; each call allocates its previews from torch's cache; medians of alternating "
+                "rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -567,7 +695,14 @@ def main():
     ap.add_argument("--frame-ranges-preview", action="store_true",
                     help="the frame_ranges_preview mode alone: the object sensor's preview with a range per frame "
                          "against the shared-range preview, a loop of single-frame calls and the whole device loop")
+    ap.add_argument("--line-frame-ranges-preview", action="store_true",
+                    help="the line_frame_ranges_preview mode alone: the line sensors' previews with a V range per "
+                         "frame against the shared-range preview, a loop of single-frame calls and the whole device "
+                         "loop")
     args = ap.parse_args()
+    if args.line_frame_ranges_preview:
+        print(json.dumps(line_frame_ranges_preview(args)))
+        return
     if args.frame_ranges_preview:
         print(json.dumps(frame_ranges_preview(args)))
         return

@@ -385,6 +385,29 @@ extern "C" int32_t trik_hsv_line_preview(TRIK_VIDTRANSCODE_CV_Handle h, const Tr
   });
 }
 
+extern "C" int32_t trik_hsv_line_frame_ranges_preview(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
+                                                      const uint16_t* ranges, const TrikHsvTargetSums* sums,
+                                                      int32_t out_width, int32_t out_height, int32_t out_line_length,
+                                                      uint8_t* previews, int64_t preview_stride, void* stream) {
+  const PreviewDst d = {out_width, out_height, out_line_length, previews, preview_stride};
+  int32_t rc = check_handle_batch(h, b);  // (either layout: it picks the line sensor)
+  if (rc) return rc;
+  if (b->n_frames > 0 && !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges is NULL");
+  if (b->n_frames > 0 && !sums) return fail(TRIK_IVIDTRANSCODE_EFAIL, "sums is NULL");
+  rc = check_preview_out(b, d, true);
+  if (rc) return rc;
+  if (b->n_frames > 0 && preview_bytes(d) > 0 && !previews) return fail(TRIK_IVIDTRANSCODE_EFAIL, "previews is NULL");
+  rc = check_device(h, b, sums);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return locked_preview(h, b, d, [&] {
+    // (the pointer's kind is asked of the runtime; its bytes are read by the kernels alone)
+    const std::string e = device_buffer_error(ranges, h->device, "ranges");
+    if (!e.empty()) return fail(TRIK_IVIDTRANSCODE_EFAIL, e);
+    return line_frame_ranges_preview_core(h, *b, ranges, sums, d, s);
+  });
+}
+
 extern "C" int32_t trik_hsv_blob_batch(TRIK_VIDTRANSCODE_CV_Handle h, const TrikHsvFrameBatch* b,
                                        const TRIK_VIDTRANSCODE_CV_OV7670_InArgsAlg* hsv, TrikHsvTarget* targets,
                                        int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,

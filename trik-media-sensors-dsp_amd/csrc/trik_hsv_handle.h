@@ -416,6 +416,11 @@ int32_t frame_ranges_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, c
 int32_t line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
                           const TRIK_VIDTRANSCODE_CV_InArgsAlg& table_range, int col_lo, int col_hi, int band,
                           const TrikHsvTargetSums* sums, const PreviewDst& d, hipStream_t s);
+// a line sensor's preview (b.layout: ov7670 with its column window and band
+// lines, or the webcam line sensor on YUYV) with frame f's V bounds at ranges +
+// 6 f + 4 in device memory (no table set; the hot-kernel report is left as it is)
+int32_t line_frame_ranges_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const uint16_t* ranges,
+                                       const TrikHsvTargetSums* sums, const PreviewDst& d, hipStream_t s);
 // the multi-blob sensor; NULL outputs go to the handle's scratch (ba tells where)
 int32_t blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b, const TRIK_VIDTRANSCODE_CV_InArgsAlg& range,
                   TrikHsvTarget* targets, int32_t* top, uint8_t* meta, uint16_t* labels, int32_t* n_labels,

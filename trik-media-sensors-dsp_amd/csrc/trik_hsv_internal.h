@@ -447,8 +447,8 @@ int launch_preview(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums
 // a.guides_drawn, then the circle from sums[f * sums_pitch])
 int launch_preview_overlay(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
 // the 2:1 row kernels' conditions on maps, layout, alignment and sizes
-// (trik_hsv_operator.hip): the one predicate of launch_preview's and
-// launch_frame_ranges_preview's 2:1 forms
+// (trik_hsv_operator.hip): the one predicate of launch_preview's,
+// launch_frame_ranges_preview's and launch_line_frame_ranges_preview's 2:1 forms
 bool preview_rows2_ok(const PreviewArgs& a);
 // The object sensor's preview with an HSV range PER FRAME, read on the device
 // (trik_hsv_frame_ranges_preview.hip; no table, a.tables and a.range are not
@@ -471,6 +471,13 @@ int launch_preview_rows2(const PreviewArgs& a, hipStream_t s);
 // a line sensor's whole preview: body and overlay (band = 1: the ov7670 line
 // sensor's band lines), fused into one pass where the 2:1 kernel applies
 int launch_line_preview(PreviewArgs a, const TrikHsvTargetSums* sums, int band, hipStream_t s);
+// The line sensors' previews with a V range PER FRAME, read on the device
+// (trik_hsv_line_frame_ranges_preview.hip; no table, a.tables and a.range are
+// not read): frame f under entries 4 and 5 of ranges + 6 f in percent, the
+// overlays with sums[f]; a.layout picks the sensor (ov7670: band lines, and the
+// caller's maps carry its column window; YUYV: the webcam line sensor).
+int launch_line_frame_ranges_preview(const PreviewArgs& a, const uint16_t* ranges, const TrikHsvTargetSums* sums,
+                                     hipStream_t s);
 
 // ov7670 multi-blob sensor of N frames (trik_hsv_blob.hip).
 struct BlobArgs : FrameView {

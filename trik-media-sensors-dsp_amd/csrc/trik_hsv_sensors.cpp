@@ -348,6 +348,19 @@ int32_t trik_hsv::line_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
   return note_uses(h, set, true, s);
 }
 
+// the handle lends its maps only, with the layout's column window (LSEQ:283:
+// columns 5..W-5; LSEQW:232: every column)
+int32_t trik_hsv::line_frame_ranges_preview_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
+                                                 const uint16_t* ranges, const TrikHsvTargetSums* sums,
+                                                 const PreviewDst& d, hipStream_t s) {
+  const bool ov7670 = b.layout == TRIK_HSV_LAYOUT_OV7670;
+  const int32_t rc = ensure_maps(h, b.width, b.height, d.out_w, d.out_h, s, ov7670 ? 5 : 0,
+                                 ov7670 ? b.width - 5 : 0x7FFFFFFF);
+  if (rc) return rc;
+  HIP_TRY(launch_line_frame_ranges_preview(preview_args(h, b, d), ranges, sums, s));
+  return note_uses(h, nullptr, true, s);
+}
+
 int32_t trik_hsv::blob_core(TrikCvHandle* h, const TrikHsvFrameBatch& b,
                             const TRIK_VIDTRANSCODE_CV_InArgsAlg& range, TrikHsvTarget* targets, int32_t* top,
                             uint8_t* meta, uint16_t* labels, int32_t* n_labels, hipStream_t s, BlobArgs& ba) {

@@ -77,15 +77,21 @@ def _ptr(t) -> C.c_void_p:
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _preview_dims(b, out_width, out_height, out_line_length):
+    """(out_width, out_height, out_line_length) with their defaults: half the
+    frame, two bytes per pixel."""
+    ow = b.width // 2 if out_width is None else out_width
+    oh = b.height // 2 if out_height is None else out_height
+    return ow, oh, 2 * ow if out_line_length is None else out_line_length
+
+
 def _preview_out(b, frames, out_width, out_height, out_line_length):
     """A preview call's output: (out_width, out_height, out_line_length) with
     their defaults (half the frame, two bytes per pixel) and the previews
     tensor uint8 [N, out_height, out_line_length]; its stride is oh * oll."""
     import torch
 
-    ow = b.width // 2 if out_width is None else out_width
-    oh = b.height // 2 if out_height is None else out_height
-    oll = 2 * ow if out_line_length is None else out_line_length
+    ow, oh, oll = _preview_dims(b, out_width, out_height, out_line_length)
     return ow, oh, oll, torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
 
 
@@ -446,6 +452,48 @@ class Detector(_HotKernel):
                                         C.c_void_p(previews.data_ptr()), oh * oll, _stream_ptr(stream, frames))
         if rc:
             raise TrikHsvError(rc, "trik_hsv_line_preview")
+        return previews
+
+    def line_frame_ranges_preview(self, frames, width, height, line_length, layout, ranges, sums, *,
+                                  out_width=None, out_height=None, out_line_length=None, n_frames=None,
+                                  frame_stride=None, previews=None, preview_stride=None, stream=None):
+        """Line-sensor previews (uint8 [N, out_height, out_line_length]) with a V
+        range per frame (trik_hsv_line_frame_ranges_preview): LAYOUT_OV7670 is
+        the ov7670 line sensor's picture, LAYOUT_YUYV the webcam line sensor's.
+        `ranges` is line_frame_ranges_batch's CUDA tensor [N, 6] (or [N, 1, 6])
+        of int16 / uint16, entries 4 and 5 read by the kernels in stream order;
+        `sums` its sums [N, 3] (int64), whose frame f gives the target line.
+        `previews`: a uint8 CUDA tensor to write into instead of a new one,
+        preview f at byte f * preview_stride (default out_height *
+        out_line_length); it is returned as it is."""
+        import torch
+
+        b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+        if (not isinstance(ranges, torch.Tensor) or not ranges.is_cuda or ranges.dtype.itemsize != 2
+                or ranges.dtype.is_floating_point or not ranges.is_contiguous()
+                or tuple(ranges.shape) not in ((b.n_frames, 6), (b.n_frames, 1, 6))):
+            raise ValueError("ranges must be a contiguous CUDA (HIP) tensor [n_frames, 6] of int16 or uint16")
+        if (not isinstance(sums, torch.Tensor) or not sums.is_cuda or sums.dtype != torch.int64
+                or not sums.is_contiguous() or sums.numel() != 3 * b.n_frames):
+            raise ValueError("sums must be a contiguous CUDA (HIP) int64 tensor [n_frames, 3]")
+        ow, oh, oll = _preview_dims(b, out_width, out_height, out_line_length)
+        stride = oh * oll if preview_stride is None else int(preview_stride)
+        if previews is None:
+            if stride != oh * oll:
+                raise ValueError("preview_stride needs the previews tensor it strides over")
+            previews = torch.empty((b.n_frames, oh, oll), dtype=torch.uint8, device=frames.device)
+        else:
+            need = (b.n_frames - 1) * stride + oh * oll if b.n_frames > 0 else 0
+            if (not isinstance(previews, torch.Tensor) or not previews.is_cuda or previews.dtype != torch.uint8
+                    or not previews.is_contiguous() or stride < oh * oll or previews.numel() < need):
+                raise ValueError("previews must be a contiguous CUDA (HIP) uint8 tensor of at least "
+                                 "(n_frames - 1) * preview_stride + out_height * out_line_length bytes")
+        rc = _lib.trik_hsv_line_frame_ranges_preview(self._h, C.byref(b), C.c_void_p(ranges.data_ptr()),
+                                                     C.c_void_p(sums.data_ptr()), ow, oh, oll,
+                                                     C.c_void_p(previews.data_ptr()), stride,
+                                                     _stream_ptr(stream, frames))
+        if rc:
+            raise TrikHsvError(rc, "trik_hsv_line_frame_ranges_preview")
         return previews
 
 

@@ -250,7 +250,9 @@ PROTOTYPES = {
                                        i32, i32, i32, C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_line_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,
                                C.c_void_p, C.c_int64, C.c_void_p], i32),
-    "trik_hsv_blob_batch": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(OV7670InArgsAlg), C.c_void_p,
+    "trik_hsv_line_frame_ranges_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, C.c_void_p, i32, i32, i32,
+                                            C.c_void_p, C.c_int64, C.c_void_p], i32),
+    "trik_hsv_blob_batch":([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(OV7670InArgsAlg), C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),
     "trik_hsv_blob_batch_ranges": ([C.c_void_p, C.POINTER(FrameBatch), C.POINTER(InArgsAlg), i32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], i32),

@@ -829,6 +829,48 @@ int32_t trik_hsv_frame_ranges_batch(const TrikHsvFrameBatch* batch, const uint16
 int32_t trik_hsv_ranges_of_detect(const uint16_t* detect_dev, int32_t n, uint16_t* ranges_dev, int32_t n_ranges,
                                   int32_t t, void* hip_stream);
 
+/* The reference's RGB888/HSV image as an output: what convertImageYuyvToHsv
+ * leaves in s_rgb888hsv (WSEQ:251-284, OSEQ:343-387, and the line, MxN and
+ * edge copies), the first two stages of every sensor, for N frames, bit for
+ * bit on every (Y, U, V) -- the image every other call computes and none hands
+ * out.  Chroma as everywhere else: per YUYV word for packed frames; U from the
+ * odd chroma byte and V from the even one for the ov7670 planes. */
+#define TRIK_HSV_CONVERT_RGB888HSV  0  /* uint64 per pixel: ((uint64)0x00RRGGBB << 32) | 0x00VVSSHH,
+                                          the s_rgb888hsv entry (_itoll(rgb, hsv), WSEQ:243-247), little-endian */
+#define TRIK_HSV_CONVERT_HSV_PLANES 1  /* three uint8 planes per frame: H, S, V */
+#define TRIK_HSV_CONVERT_RGB_PLANES 2  /* three uint8 planes per frame: R, G, B */
+
+typedef struct TrikHsvConvertOut {
+  void*   out;           /* device */
+  int64_t frame_stride;  /* bytes from frame f to f + 1 */
+  int64_t plane_stride;  /* bytes from plane p to p + 1 (ignored by form 0) */
+  int32_t row_pitch;     /* bytes from row r to r + 1 */
+  int32_t form;
+} TrikHsvConvertOut;
+
+/* Pixel (f, r, c) of form 0 is the 8 bytes at out + f*frame_stride +
+ * r*row_pitch + 8*c; byte (f, p, r, c) of a planar form is at out +
+ * f*frame_stride + p*plane_stride + r*row_pitch + c.  Only these bytes are
+ * written: the bytes of a row past its pixels (pitch padding), between planes
+ * and between frames are left as they are (the reference's buffer is dense
+ * and static; the strides are this call's own surface).
+ * Both layouts and every geometry the other batched calls take: width % 32
+ * == 0, height % 4 == 0, padded line_length, odd frame_stride, a misaligned
+ * base.  A misaligned out, or a stride or pitch that is no multiple of 16, is
+ * no error: like misaligned frames it takes the slower kernel (a lane per
+ * pixel instead of 16-byte loads and stores).
+ * No handle: nothing depends on a range.  Stream-ordered, no host
+ * synchronisation: frames written earlier on the stream are the ones
+ * converted.  n_frames == 0 returns 0 and touches nothing; width or height 0
+ * returns 0 and writes nothing.  Fails (trik_hsv_last_error()) and enqueues
+ * nothing for a NULL batch or out; NULL frames or out->out when n_frames > 0;
+ * an unknown layout or form; a geometry the other batched calls refuse;
+ * row_pitch below the row's bytes (8*width for form 0, width for the planes);
+ * plane_stride < height*row_pitch for a planar form; frame_stride below the
+ * frame's extent (height*row_pitch for form 0, 2*plane_stride +
+ * height*row_pitch for the planes; checked for a single frame too). */
+int32_t trik_hsv_convert_batch(const TrikHsvFrameBatch* batch, const TrikHsvConvertOut* out, void* hip_stream);
+
 /* The object sensor's preview for N frames with an HSV range PER FRAME, read
  * from device memory by the kernels: the operator's picture of what
  * trik_hsv_frame_ranges_batch detected.

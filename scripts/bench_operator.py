@@ -68,6 +68,13 @@
               sensor); a 400x300 output through both gathers; at N = 256
               against a loop of 256 single-frame trik_hsv_line_preview calls;
               and the whole device loop of the ov7670 line kind per step.
+  convert (--convert, a run of its own)
+              trik_hsv_convert_batch: 4096 x 640x480 ov7670 scene frames and
+              their packed-YUYV twins to each of the three forms, beside (a)
+              trik_hsv_frame_ranges_batch at T = 1 on the same frames (the same
+              per-pixel arithmetic, no image written) and (b) a device-to-device
+              Tensor.copy_ that moves as many bytes as the form reads plus
+              writes; the bound is each form <= 1.1 x ((a) + (b)).
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -669,6 +676,86 @@ def line_frame_ranges_preview(args):
                 "rounds, all in one process"}}
 
 
+def convert(args):
+    """trik_hsv_convert_batch on 640x480 scene frames of both layouts, each
+    form, alternating in this process with
+      (a) trik_hsv_frame_ranges_batch at T = 1 on the same frames: the same
+          per-pixel arithmetic and the same bytes read, no image written, and
+      (b) a device-to-device Tensor.copy_ whose bytes read plus bytes written
+          equal the form's (a copy of 5 B/px for the 64-bit form, which reads 2
+          and writes 8; of 2.5 B/px for the planes, which read 2 and write 3).
+    Algorithmic bytes = the frames once plus the image once.  The bound: a form's
+    time <= 1.1 x ((a) + (b)) of the same run -- converting and writing in one
+    pass is no slower than doing them one after the other."""
+    import torch
+
+    import trik_hsv
+
+    W, H, F = 640, 480, args.frames
+    px = F * W * H
+    ov, yuyv = scene_frames_and_twins(F, W, H)
+    stream = torch.cuda.current_stream()
+    forms = {"rgb888hsv": trik_hsv.CONVERT_RGB888HSV, "hsv_planes": trik_hsv.CONVERT_HSV_PLANES,
+             "rgb_planes": trik_hsv.CONVERT_RGB_PLANES}
+    layouts = {"ov7670": (ov, W, trik_hsv.LAYOUT_OV7670), "yuyv": (yuyv, 2 * W, trik_hsv.LAYOUT_YUYV)}
+    outs = {"rgb888hsv": torch.empty((F, H, W), dtype=torch.int64, device="cuda"),
+            "planes": torch.empty((F, 3, H, W), dtype=torch.uint8, device="cuda")}
+    one_range = torch.tensor([[(0, 30, 50, 100, 30, 100)]] * F, dtype=torch.int16, device="cuda")
+    copy_bytes = {"rgb888hsv": 5 * px, "planes": 5 * px // 2}
+    src = torch.empty(copy_bytes["rgb888hsv"], dtype=torch.uint8, device="cuda").fill_(7)
+    dst = torch.empty_like(src)
+    fns = {}
+    for lname, (frames, ll, layout) in layouts.items():
+        fns[f"frame_ranges_T1_{lname}"] = (lambda fr=frames, ll=ll, lay=layout:
+                                           trik_hsv.frame_ranges_batch(fr, W, H, ll, lay, one_range))
+        for fname, form in forms.items():
+            o = outs["rgb888hsv" if fname == "rgb888hsv" else "planes"]
+            fns[f"{fname}_{lname}"] = (lambda fr=frames, ll=ll, lay=layout, form=form, o=o:
+                                       trik_hsv.convert_batch(fr, W, H, ll, lay, form, out=o))
+    for cname, nb in copy_bytes.items():
+        fns[f"copy_{cname}"] = lambda nb=nb: dst[:nb].copy_(src[:nb])
+    # both layouts hold the same (Y, U, V) at every pixel: the same image
+    same = all(torch.equal(trik_hsv.convert_batch(ov[:8 * 2 * H * W], W, H, W, trik_hsv.LAYOUT_OV7670, f),
+                           trik_hsv.convert_batch(yuyv[:8 * 2 * H * W], W, H, 2 * W, trik_hsv.LAYOUT_YUYV, f))
+               for f in forms.values())
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name, fn in fns.items():
+            runs[name].append(timed(fn, stream, args.iters))
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name, nb):
+        return {"ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]], "bytes_algorithmic": nb,
+                "achieved_GBs": round(nb / (med[name] / 1e3) / 1e9, 1),
+                "hbm_frac": round(nb / (med[name] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+    out = {}
+    for lname in layouts:
+        out[f"frame_ranges_T1_{lname}"] = row(f"frame_ranges_T1_{lname}", 2 * px)
+    for cname, nb in copy_bytes.items():
+        out[f"copy_{cname}"] = row(f"copy_{cname}", 2 * nb)
+    ok = True
+    for lname in layouts:
+        for fname in forms:
+            cname = "rgb888hsv" if fname == "rgb888hsv" else "planes"
+            name = f"{fname}_{lname}"
+            r = row(name, 2 * copy_bytes[cname])
+            r["Mframes_per_s"] = round(F / med[name] / 1e3, 3)
+            bound = 1.1 * (med[f"frame_ranges_T1_{lname}"] + med[f"copy_{cname}"])
+            r["bound_ms"] = round(bound, 4)
+            r["over_bound"] = round(med[name] / bound, 3)
+            r["within_bound"] = bool(med[name] <= bound)
+            ok = ok and r["within_bound"]
+            out[name] = r
+    return {"convert": {
+        "frames": F, "geometry": [W, H], "scene_frames": True, "iters": args.iters, "rounds": args.rounds,
+        "layouts_give_the_same_image": bool(same), "all_within_bound": bool(ok), **out,
+        "note": "<form>_<layout>: trik_hsv_convert_batch into a dense tensor (convert_vec_kernel); bytes = frames read "
+                "(2 B/px) + image written (8 or 3 B/px); frame_ranges_T1_*: memset + frame_ranges_kernel + "
+                "targets_kernel; copy_*: Tensor.copy_ of half the form's bytes (read + written = the form's); "
+                "bound_ms = 1.1 x (frame_ranges_T1 + copy); medians of alternating rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -699,7 +786,13 @@ def main():
                     help="the line_frame_ranges_preview mode alone: the line sensors' previews with a V range per "
                          "frame against the shared-range preview, a loop of single-frame calls and the whole device "
                          "loop")
+    ap.add_argument("--convert", action="store_true",
+                    help="the convert mode alone: trik_hsv_convert_batch, each form and layout, against the per-frame "
+                         "sums at T = 1 plus a device-to-device copy of the same bytes")
     args = ap.parse_args()
+    if args.convert:
+        print(json.dumps(convert(args)))
+        return
     if args.line_frame_ranges_preview:
         print(json.dumps(line_frame_ranges_preview(args)))
         return

@@ -336,6 +336,30 @@ extern "C" int32_t trik_hsv_frame_ranges_batch(const TrikHsvFrameBatch* b, const
   return 0;
 }
 
+extern "C" int32_t trik_hsv_convert_batch(const TrikHsvFrameBatch* b, const TrikHsvConvertOut* o, void* stream) {
+  if (!o) return fail(TRIK_IVIDTRANSCODE_EFAIL, "convert_batch: out is NULL");
+  const int32_t rc = check_batch(b);
+  if (rc) return rc;
+  if (o->form != TRIK_HSV_CONVERT_RGB888HSV && o->form != TRIK_HSV_CONVERT_HSV_PLANES &&
+      o->form != TRIK_HSV_CONVERT_RGB_PLANES)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "convert_batch: unknown form " + std::to_string(o->form));
+  if (b->n_frames > 0 && !b->frames) return fail(TRIK_IVIDTRANSCODE_EFAIL, "frames is NULL");
+  if (b->n_frames > 0 && !o->out) return fail(TRIK_IVIDTRANSCODE_EFAIL, "convert_batch: out->out is NULL");
+  const bool planes = o->form != TRIK_HSV_CONVERT_RGB888HSV;
+  if (o->row_pitch < (planes ? 1 : 8) * (int64_t)b->width)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "convert_batch: row_pitch shorter than a row (8*width, or width for planes)");
+  const int64_t image = (int64_t)b->height * o->row_pitch;
+  if (planes && o->plane_stride < image)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "convert_batch: plane_stride smaller than a plane (height*row_pitch)");
+  // (plane_stride >= 0 here, and below 2^62 or the sum would not be below frame_stride)
+  if (planes ? o->plane_stride > (INT64_MAX - image) / 2 || o->frame_stride < 2 * o->plane_stride + image
+             : o->frame_stride < image)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "convert_batch: frame_stride smaller than a frame's output");
+  if (b->n_frames == 0 || b->width == 0 || b->height == 0) return 0;  // nothing is written
+  HIP_TRY(launch_convert(*b, *o, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
 extern "C" int32_t trik_hsv_ranges_of_detect(const uint16_t* detect, int32_t n, uint16_t* ranges, int32_t n_ranges,
                                              int32_t t, void* stream) {
   if (n < 0) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges_of_detect: n < 0");

@@ -441,6 +441,11 @@ int launch_frame_ranges(const TrikHsvFrameBatch& b, const uint16_t* ranges, int 
                         hipStream_t s);
 // detect[i][6] (centre, tolerance) -> ranges[i][n_ranges][6]'s entry t (BMB:110-130)
 int launch_ranges_of_detect(const uint16_t* detect, int n, uint16_t* ranges, int n_ranges, int t, hipStream_t s);
+// The RGB888/HSV image of every frame in o's form (trik_hsv_convert.hip); b and
+// o validated, with n_frames, width and height > 0.  convert_vec_ok: the one
+// predicate of its kernel choice (16-byte aligned input and output).
+bool convert_vec_ok(const TrikHsvFrameBatch& b, const TrikHsvConvertOut& o);
+int launch_convert(const TrikHsvFrameBatch& b, const TrikHsvConvertOut& o, hipStream_t s);
 // preview_kernel then overlay_kernel (circle from sums[f * sums_pitch])
 int launch_preview(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
 // launch_preview's last kernel alone: overlay_kernel (the guide lines unless

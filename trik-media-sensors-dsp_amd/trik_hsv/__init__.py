@@ -17,7 +17,7 @@ import ctypes as C
 from typing import Iterable, Sequence, Tuple
 
 from . import _abi
-from ._abi import (FORMAT_RGB565X, FORMAT_UNKNOWN, FORMAT_YUV422, FORMAT_YUV422P,  # noqa: F401
+from ._abi import (CONVERT_HSV_PLANES, CONVERT_RGB888HSV, CONVERT_RGB_PLANES, FORMAT_RGB565X, FORMAT_UNKNOWN, FORMAT_YUV422, FORMAT_YUV422P,  # noqa: F401
                    IALG_EFAIL, IALG_EOK, IVIDTRANSCODE_EFAIL, IVIDTRANSCODE_EOK,
                    IVIDTRANSCODE_EUNSUPPORTED, LAYOUT_OV7670, LAYOUT_YUYV, XDM_FLUSH,
                    XDM_GETBUFINFO, XDM_GETSTATUS, XDM_GETVERSION, XDM_RESET, XDM_SETDEFAULT,
@@ -607,6 +607,41 @@ def frame_ranges_batch(frames, width, height, line_length, layout, ranges, *, n_
     if rc:
         raise TrikHsvError(rc, "trik_hsv_frame_ranges_batch")
     return sums, targets
+
+
+def convert_batch(frames, width, height, line_length, layout, form=CONVERT_HSV_PLANES, *, out=None, n_frames=None,
+                  frame_stride=None, stream=None):
+    """The reference's RGB888/HSV image of every frame (trik_hsv_convert_batch),
+    bit for bit.  CONVERT_RGB888HSV: int64 [N, H, W], each value the
+    s_rgb888hsv entry 0x00RRGGBB << 32 | 0x00VVSSHH.  CONVERT_HSV_PLANES /
+    CONVERT_RGB_PLANES: uint8 [N, 3, H, W], planes H, S, V / R, G, B.  Returns
+    a dense tensor it allocates, or fills `out` (a CUDA tensor of that shape and
+    dtype whose last axis is contiguous; its other strides are taken as they
+    are, and the elements between its rows, planes and frames are not
+    written)."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+    planes = form != CONVERT_RGB888HSV
+    shape = (b.n_frames, 3, height, width) if planes else (b.n_frames, height, width)
+    dtype = torch.uint8 if planes else torch.int64
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=frames.device)
+    elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or (width > 1 and out.stride(-1) != 1):
+        raise ValueError(f"out must be a CUDA (HIP) {dtype} tensor of shape {shape} with a contiguous last axis")
+    if out.numel() == 0:  # no frame or no pixel: the call writes nothing (and an empty tensor has no address)
+        return out
+    item = out.element_size()
+    st = [s * item for s in out.stride()]
+    # (the stride of an axis of length 0 or 1 addresses nothing: the dense one stands for it)
+    row = st[-2] if height > 1 else width * item
+    plane = (st[1] if planes else 0)
+    frame = st[0] if b.n_frames > 1 else (2 * plane if planes else 0) + height * row
+    o = _abi.ConvertOut(out.data_ptr(), frame, plane, row, int(form))
+    rc = _lib.trik_hsv_convert_batch(C.byref(b), C.byref(o), _stream_ptr(stream, frames))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_convert_batch")
+    return out
 
 
 def ranges_of_detect(detect, *, ranges=None, n_ranges=1, t=0, stream=None):

@@ -37,6 +37,7 @@ MAX_IO_BUFFERS = 16
 LAYOUT_YUYV = 0
 LAYOUT_OV7670 = 1
 MAX_RANGES = 64
+CONVERT_RGB888HSV, CONVERT_HSV_PLANES, CONVERT_RGB_PLANES = 0, 1, 2  # TRIK_HSV_CONVERT_*
 BLOB_CHUNK_SLOTS = 4096  # TRIK_HSV_BLOB_CHUNK_SLOTS
 
 i32, i64, u8, u16, u64 = C.c_int32, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint64
@@ -194,6 +195,11 @@ class FrameBatch(C.Structure):
                 ("width", i32), ("height", i32), ("line_length", i32), ("layout", i32)]
 
 
+class ConvertOut(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("frame_stride", i64), ("plane_stride", i64), ("row_pitch", i32),
+                ("form", i32)]
+
+
 class TargetSums(C.Structure):
     _fields_ = [("points", i64), ("sum_x", i64), ("sum_y", i64)]
 
@@ -246,6 +252,7 @@ PROTOTYPES = {
     "trik_hsv_frame_ranges_batch": ([C.POINTER(FrameBatch), C.c_void_p, i32, C.c_void_p, C.c_void_p,
                                      C.c_void_p], i32),
     "trik_hsv_ranges_of_detect": ([C.c_void_p, i32, C.c_void_p, i32, i32, C.c_void_p], i32),
+    "trik_hsv_convert_batch": ([C.POINTER(FrameBatch), C.POINTER(ConvertOut), C.c_void_p], i32),
     "trik_hsv_frame_ranges_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, i32, i32, C.c_void_p, i32,
                                        i32, i32, i32, C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_line_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,

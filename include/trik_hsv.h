@@ -871,6 +871,61 @@ typedef struct TrikHsvConvertOut {
  * height*row_pitch for the planes; checked for a single frame too). */
 int32_t trik_hsv_convert_batch(const TrikHsvFrameBatch* batch, const TrikHsvConvertOut* out, void* hip_stream);
 
+/* The per-pixel detection mask as an output: the reference's detectHsvPixel
+ * (WSEQ:171-179) on every pixel's s_rgb888hsv entry under range t of the
+ * pixel's frame, bit for bit -- the "detected" image every sensor computes and
+ * hands out only summed (sums, targets), reduced (4x4 metapixels) or drawn
+ * (previews).  One plane per range. */
+#define TRIK_HSV_MASK_BITS  0  /* n_ranges bit planes per frame; pixel c of row r is bit (c & 7)
+                                  of byte c >> 3 of its row, least significant bit first
+                                  (= bit c & 31 of little-endian uint32 c >> 5) */
+#define TRIK_HSV_MASK_BYTES 1  /* n_ranges byte planes per frame; 0xFF detected, 0x00 not */
+
+typedef struct TrikHsvMaskOut {
+  void*   out;           /* device */
+  int64_t frame_stride;  /* bytes from frame f to f + 1 */
+  int64_t plane_stride;  /* bytes from range t's plane to range t + 1's */
+  int32_t row_pitch;     /* bytes from row r to r + 1 */
+  int32_t form;
+} TrikHsvMaskOut;
+
+/* Range t of frame f is the six-tuple at ranges_dev + f*ranges_frame_stride +
+ * 6*t: uint16 in InArgs units (hueFrom, hueTo, satFrom, satTo, valFrom, valTo),
+ * exactly the tuples of trik_hsv_frame_ranges_batch.  ranges_frame_stride
+ * counts uint16 elements: 0 is one shared set of n_ranges tuples for every
+ * frame; 6*n_ranges is the buffer trik_hsv_frame_ranges_batch and
+ * trik_hsv_ranges_of_detect use, taken as it is; larger values skip the
+ * elements between the sets; 1 .. 6*n_ranges-1 and negative values fail.
+ * n_ranges is 1..TRIK_HSV_MAX_RANGES.  The host never dereferences ranges_dev,
+ * the kernel reads it when it runs, so a producer earlier on the stream is
+ * seen.  The tuples are scaled and packed as WSEQ:425-445 does, in int32 (the
+ * packing of trik_hsv_frame_ranges_batch): a saturation or value above 255
+ * behaves as 255.
+ * Byte b of row r of plane t of frame f is at out + f*frame_stride +
+ * t*plane_stride + r*row_pitch + b, with b < width/8 (bits) or b < width
+ * (bytes).  Only these bytes are written, each exactly once per call, by plain
+ * stores (no atomics, no read-modify-write): row padding and the bytes between
+ * planes and between frames keep what they held, and the caller need not zero
+ * anything.  The value is bit t of the mask trik_hsv_batch_masks gives for the
+ * same ranges (any t up to 63 here).
+ * Both layouts and every geometry and placement trik_hsv_frame_ranges_batch
+ * takes: width % 32 == 0 (a bit row is whole 32-bit words), height % 4 == 0,
+ * padded line_length, odd frame_stride, a misaligned base.  A misaligned out,
+ * stride or pitch is no error: it takes the slower kernel (the fast one needs
+ * 16-byte aligned frames, and out, row_pitch, plane_stride when n_ranges > 1
+ * and frame_stride when n_frames > 1 as multiples of 4 for the bits, 8 for the
+ * bytes).  Planes cannot interleave by rows: plane_stride >= height*row_pitch.
+ * No handle, no table per range set.  Stream-ordered, no host synchronisation.
+ * n_frames == 0 returns 0 and touches nothing; width or height 0 returns 0 and
+ * writes nothing.  Fails (trik_hsv_last_error()) and enqueues nothing for a
+ * NULL batch or out; NULL frames, ranges_dev or out->out when n_frames > 0; an
+ * unknown layout or form; a geometry the other batched calls refuse; n_ranges
+ * or ranges_frame_stride out of bounds; row_pitch below the row's bytes;
+ * plane_stride < height*row_pitch; frame_stride < (n_ranges-1)*plane_stride +
+ * height*row_pitch (checked for a single frame too). */
+int32_t trik_hsv_mask_batch(const TrikHsvFrameBatch* batch, const uint16_t* ranges_dev, int32_t n_ranges,
+                            int64_t ranges_frame_stride, const TrikHsvMaskOut* out, void* hip_stream);
+
 /* The object sensor's preview for N frames with an HSV range PER FRAME, read
  * from device memory by the kernels: the operator's picture of what
  * trik_hsv_frame_ranges_batch detected.

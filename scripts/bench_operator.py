@@ -75,6 +75,15 @@
               per-pixel arithmetic, no image written) and (b) a device-to-device
               Tensor.copy_ that moves as many bytes as the form reads plus
               writes; the bound is each form <= 1.1 x ((a) + (b)).
+  mask (--mask, a run of its own)
+              trik_hsv_mask_batch with a range set per frame: 4096 x 640x480
+              ov7670 scene frames and their packed-YUYV twins to bit planes at
+              T = 1 and T = 4 and to a byte plane at T = 1, beside (a)
+              trik_hsv_frame_ranges_batch at the same T (the same arithmetic, no
+              image written), (b) a device-to-device Tensor.copy_ of the mask's
+              byte count and, for information, trik_hsv_batch_masks with one
+              shared range; the aim is each form <= 1.1 x ((a) + (b)).  And at
+              N = 256 against a loop of 256 single-frame calls.
 
 Prints one JSON object.  usage: python scripts/bench_operator.py [--frames N]
 """
@@ -756,6 +765,118 @@ def convert(args):
                 "bound_ms = 1.1 x (frame_ranges_T1 + copy); medians of alternating rounds, all in one process"}}
 
 
+def mask(args):
+    """trik_hsv_mask_batch on 640x480 scene frames of both layouts with a range
+    set per frame (the four bench ranges, rotated by the frame): bit planes at
+    T = 1 and T = 4, a byte plane at T = 1, alternating in this process with
+      (a) trik_hsv_frame_ranges_batch at the same T on the same frames and
+          ranges: the same per-pixel arithmetic and bytes read, no image written,
+      (b) a device-to-device Tensor.copy_ of the mask's byte count, and
+      (c) for information, trik_hsv_batch_masks with one shared range (a handle,
+          its tables, a byte per pixel with the ranges in its bits).
+    Algorithmic bytes = the frames once plus the mask once.  The aim: a form's
+    time <= 1.1 x ((a) + (b)) of the same run.  At N = 256 the T = 4 bit planes
+    with 256 range sets against 256 single-frame calls of the same entry point."""
+    import torch
+
+    import trik_hsv
+
+    W, H, F, FB = 640, 480, args.frames, 256
+    px = F * W * H
+    ov, yuyv = scene_frames_and_twins(F, W, H)
+    stream = torch.cuda.current_stream()
+    R4 = [(0, 30, 50, 100, 30, 100), (90, 150, 40, 100, 20, 100), (200, 260, 40, 100, 20, 100),
+          (330, 20, 30, 100, 30, 100)]
+    ranges = {t: torch.tensor([[R4[(f + k) % 4] for k in range(t)] for f in range(F)], dtype=torch.int16, device="cuda")
+              for t in (1, 4)}
+    layouts = {"ov7670": (ov, W, trik_hsv.LAYOUT_OV7670), "yuyv": (yuyv, 2 * W, trik_hsv.LAYOUT_YUYV)}
+    forms = {"bits_T1": (trik_hsv.MASK_BITS, 1), "bits_T4": (trik_hsv.MASK_BITS, 4), "bytes_T1": (trik_hsv.MASK_BYTES, 1)}
+    mask_bytes = {"bits_T1": px // 8, "bits_T4": px // 2, "bytes_T1": px}
+    outs = {k: torch.empty((F, t, H, W // 8 if form == trik_hsv.MASK_BITS else W), dtype=torch.uint8, device="cuda")
+            for k, (form, t) in forms.items()}
+    src = torch.empty(px, dtype=torch.uint8, device="cuda").fill_(7)
+    dst = torch.empty_like(src)
+    det = trik_hsv.Detector()
+    fns = {}
+    for lname, (frames, ll, layout) in layouts.items():
+        for t in (1, 4):
+            fns[f"frame_ranges_T{t}_{lname}"] = (lambda fr=frames, ll=ll, lay=layout, t=t:
+                                                 trik_hsv.frame_ranges_batch(fr, W, H, ll, lay, ranges[t]))
+        for fname, (form, t) in forms.items():
+            fns[f"mask_{fname}_{lname}"] = (lambda fr=frames, ll=ll, lay=layout, form=form, t=t, o=outs[fname]:
+                                            trik_hsv.mask_batch(fr, W, H, ll, lay, ranges[t], form, out=o))
+        fns[f"batch_masks_shared_T1_{lname}"] = (lambda fr=frames, ll=ll, lay=layout:
+                                                 det.batch_masks(fr, W, H, ll, lay, R4[:1]))
+    for fname, nb in mask_bytes.items():
+        fns[f"copy_{fname}"] = lambda nb=nb: dst[:nb].copy_(src[:nb])
+    small = ranges[4][:FB].contiguous()
+
+    def loop256():
+        return [trik_hsv.mask_batch(yuyv[f * 2 * H * W:], W, H, 2 * W, trik_hsv.LAYOUT_YUYV, small[f], n_frames=1)
+                for f in range(FB)]
+
+    fns["mask_bits_256_T4_yuyv"] = lambda: trik_hsv.mask_batch(yuyv, W, H, 2 * W, trik_hsv.LAYOUT_YUYV, small,
+                                                               n_frames=FB)
+    fns["loop_256_T4_yuyv"] = loop256
+    # both layouts hold the same (Y, U, V) at every pixel: the same mask; the loop gives the one call's planes;
+    # bit 0 of batch_masks' byte is the byte plane of the same range
+    n8 = 8 * 2 * H * W
+    same = all(torch.equal(trik_hsv.mask_batch(ov[:n8], W, H, W, trik_hsv.LAYOUT_OV7670, ranges[t][:8], form),
+                           trik_hsv.mask_batch(yuyv[:n8], W, H, 2 * W, trik_hsv.LAYOUT_YUYV, ranges[t][:8], form))
+               for form, t in forms.values())
+    one, singles = fns["mask_bits_256_T4_yuyv"](), loop256()
+    same_256 = all(torch.equal(one[f], singles[f][0]) for f in range(FB))
+    old = det.batch_masks(yuyv[:n8], W, H, 2 * W, trik_hsv.LAYOUT_YUYV, R4[:1])[0]
+    new = trik_hsv.mask_batch(yuyv[:n8], W, H, 2 * W, trik_hsv.LAYOUT_YUYV, [R4[0]], trik_hsv.MASK_BYTES)
+    same_old = torch.equal((old & 1) * 255, new[:, 0])
+    runs = {k: [] for k in fns}
+    for _ in range(args.rounds):
+        for name, fn in fns.items():
+            runs[name].append(timed(fn, stream, 2 if name.startswith("loop_256") else args.iters))
+    det.close()
+    med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
+
+    def row(name, nb):
+        return {"ms": round(med[name], 4), "ms_runs": [round(x, 4) for x in runs[name]], "bytes_algorithmic": nb,
+                "achieved_GBs": round(nb / (med[name] / 1e3) / 1e9, 1),
+                "hbm_frac": round(nb / (med[name] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+    out = {}
+    for lname in layouts:
+        for t in (1, 4):
+            out[f"frame_ranges_T{t}_{lname}"] = row(f"frame_ranges_T{t}_{lname}", 2 * px)
+        out[f"batch_masks_shared_T1_{lname}"] = row(f"batch_masks_shared_T1_{lname}", 3 * px)
+    for fname, nb in mask_bytes.items():
+        out[f"copy_{fname}"] = row(f"copy_{fname}", 2 * nb)
+    ok = True
+    for lname in layouts:
+        for fname, (form, t) in forms.items():
+            name = f"mask_{fname}_{lname}"
+            r = row(name, 2 * px + mask_bytes[fname])
+            r["Mframes_per_s"] = round(F / med[name] / 1e3, 3)
+            bound = 1.1 * (med[f"frame_ranges_T{t}_{lname}"] + med[f"copy_{fname}"])
+            r["bound_ms"] = round(bound, 4)
+            r["over_bound"] = round(med[name] / bound, 3)
+            r["within_bound"] = bool(med[name] <= bound)
+            ok = ok and r["within_bound"]
+            out[name] = r
+    px256 = FB * W * H
+    for name in ("mask_bits_256_T4_yuyv", "loop_256_T4_yuyv"):
+        out[name] = row(name, 2 * px256 + px256 // 2)
+    out["mask_bits_256_T4_yuyv"]["over_loop"] = round(med["mask_bits_256_T4_yuyv"] / med["loop_256_T4_yuyv"], 4)
+    out["loop_256_T4_yuyv"]["ms_per_call"] = round(med["loop_256_T4_yuyv"] / FB, 4)
+    return {"mask": {
+        "frames": F, "geometry": [W, H], "scene_frames": True, "iters": args.iters, "rounds": args.rounds,
+        "layouts_give_the_same_mask": bool(same), "results_identical_256": bool(same_256),
+        "byte_plane_equals_batch_masks_bit0": bool(same_old), "all_within_bound": bool(ok), **out,
+        "note": "mask_<form>_T<t>_<layout>: trik_hsv_mask_batch into a dense tensor, a range set per frame "
+                "(mask_vec_kernel); bytes = frames read (2 B/px) + mask written (T/8 or T B/px); frame_ranges_T<t>_*: "
+                "memset + frame_ranges_kernel + targets_kernel on the same ranges; copy_*: Tensor.copy_ of the mask's "
+                "byte count; bound_ms = 1.1 x (frame_ranges + copy); batch_masks_shared_T1_*: trik_hsv_batch_masks, one "
+                "shared range, information only; loop_256_T4_yuyv: 256 single-frame trik_hsv_mask_batch calls (2 timed "
+                "iterations per round); medians of alternating rounds, all in one process"}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4096)
@@ -789,7 +910,13 @@ def main():
     ap.add_argument("--convert", action="store_true",
                     help="the convert mode alone: trik_hsv_convert_batch, each form and layout, against the per-frame "
                          "sums at T = 1 plus a device-to-device copy of the same bytes")
+    ap.add_argument("--mask", action="store_true",
+                    help="the mask mode alone: trik_hsv_mask_batch, bit and byte planes with a range set per frame, "
+                         "against the per-frame sums at the same T plus a device-to-device copy of the mask's bytes")
     args = ap.parse_args()
+    if args.mask:
+        print(json.dumps(mask(args)))
+        return
     if args.convert:
         print(json.dumps(convert(args)))
         return

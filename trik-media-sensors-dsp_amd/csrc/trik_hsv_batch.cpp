@@ -360,6 +360,32 @@ extern "C" int32_t trik_hsv_convert_batch(const TrikHsvFrameBatch* b, const Trik
   return 0;
 }
 
+extern "C" int32_t trik_hsv_mask_batch(const TrikHsvFrameBatch* b, const uint16_t* ranges, int32_t n,
+                                       int64_t ranges_stride, const TrikHsvMaskOut* o, void* stream) {
+  if (!o) return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: out is NULL");
+  const int32_t rc = check_batch(b);
+  if (rc) return rc;
+  if (o->form != TRIK_HSV_MASK_BITS && o->form != TRIK_HSV_MASK_BYTES)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: unknown form " + std::to_string(o->form));
+  if (n < 1 || n > TRIK_HSV_MAX_RANGES) return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: n_ranges must be 1..64");
+  if (ranges_stride != 0 && ranges_stride < 6 * (int64_t)n)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: ranges_frame_stride must be 0 (shared) or at least 6*n_ranges");
+  if (b->n_frames > 0 && !b->frames) return fail(TRIK_IVIDTRANSCODE_EFAIL, "frames is NULL");
+  if (b->n_frames > 0 && !ranges) return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: ranges is NULL");
+  if (b->n_frames > 0 && !o->out) return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: out->out is NULL");
+  if (o->row_pitch < (o->form == TRIK_HSV_MASK_BITS ? b->width / 8 : b->width))
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: row_pitch shorter than a row (width/8 for bits, width for bytes)");
+  const int64_t image = (int64_t)b->height * o->row_pitch;
+  if (o->plane_stride < image)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: plane_stride smaller than a plane (height*row_pitch)");
+  // (plane_stride >= 0 here; the product is kept below 2^63)
+  if (o->plane_stride > (INT64_MAX - image) / n || o->frame_stride < (n - 1) * o->plane_stride + image)
+    return fail(TRIK_IVIDTRANSCODE_EFAIL, "mask_batch: frame_stride smaller than a frame's planes");
+  if (b->n_frames == 0 || b->width == 0 || b->height == 0) return 0;  // nothing is written
+  HIP_TRY(launch_mask(*b, ranges, n, ranges_stride, *o, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
 extern "C" int32_t trik_hsv_ranges_of_detect(const uint16_t* detect, int32_t n, uint16_t* ranges, int32_t n_ranges,
                                              int32_t t, void* stream) {
   if (n < 0) return fail(TRIK_IVIDTRANSCODE_EFAIL, "ranges_of_detect: n < 0");

@@ -51,48 +51,6 @@ struct FrameRangesArgs : FrameView {
   TrikHsvTargetSums* sums;  // [n_frames][n_ranges], zeroed
 };
 
-// The four YUYV words (Y0 U Y1 V) of unit `col` (pixels 8 col .. 8 col + 7) of
-// a row.  ALIGN 16: one 16-byte load (two 8-byte loads for the planes); 4:
-// dword loads; 1: bytes through fetch_yuv.  Every byte lies inside the row.
-template <int LAYOUT, int ALIGN>
-__device__ __forceinline__ void load_unit(const uint8_t* fr, int height, int line_length, int row, int col,
-                                          uint32_t w[4]) {
-  if (ALIGN == 1) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      int y0, y1, u, v, u1, v1;
-      fetch_yuv(fr, height, line_length, LAYOUT, row, 8 * col + 2 * k, y0, u, v);
-      fetch_yuv(fr, height, line_length, LAYOUT, row, 8 * col + 2 * k + 1, y1, u1, v1);
-      w[k] = (uint32_t)y0 | ((uint32_t)u << 8) | ((uint32_t)y1 << 16) | ((uint32_t)v << 24);
-    }
-  } else if (LAYOUT == TRIK_HSV_LAYOUT_YUYV) {
-    const uint8_t* p = fr + (int64_t)row * line_length + (int64_t)col * 16;
-    if (ALIGN == 16) {
-      const uint4 v = *reinterpret_cast<const uint4*>(p);
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-      const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-      w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; w[3] = q[3];
-    }
-  } else {
-    const uint8_t* py = fr + (int64_t)row * line_length + (int64_t)col * 8;
-    const uint8_t* pc = py + (int64_t)line_length * height;
-    uint32_t y[2], c[2];
-    if (ALIGN == 16) {
-      const uint2 vy = *reinterpret_cast<const uint2*>(py);
-      const uint2 vc = *reinterpret_cast<const uint2*>(pc);
-      y[0] = vy.x; y[1] = vy.y; c[0] = vc.x; c[1] = vc.y;
-    } else {
-      y[0] = reinterpret_cast<const uint32_t*>(py)[0];
-      y[1] = reinterpret_cast<const uint32_t*>(py)[1];
-      c[0] = reinterpret_cast<const uint32_t*>(pc)[0];
-      c[1] = reinterpret_cast<const uint32_t*>(pc)[1];
-    }
-    stripe_px::ov7670_words(y[0], c[0], w[0], w[1]);
-    stripe_px::ov7670_words(y[1], c[1], w[2], w[3]);
-  }
-}
-
 // One pass over the band for NR ranges from range g0 on (ranges past the
 // frame's last never match): the lanes' 64-bit sums of N, sum_x and sum_y per
 // range, reduced over the wave into red[wave].

@@ -446,6 +446,14 @@ int launch_ranges_of_detect(const uint16_t* detect, int n, uint16_t* ranges, int
 // predicate of its kernel choice (16-byte aligned input and output).
 bool convert_vec_ok(const TrikHsvFrameBatch& b, const TrikHsvConvertOut& o);
 int launch_convert(const TrikHsvFrameBatch& b, const TrikHsvConvertOut& o, hipStream_t s);
+// The detection mask of every frame in o's form (trik_hsv_mask.hip): range t of
+// frame f is the six-tuple at ranges + f * ranges_stride + 6 t (device memory,
+// InArgs units, ranges_stride 0 or >= 6 n_ranges); b and o validated, with
+// n_frames, width and height > 0.  mask_vec_ok: the one predicate of its kernel
+// choice (16-byte aligned input, output aligned to the store's 4 or 8 bytes).
+bool mask_vec_ok(const TrikHsvFrameBatch& b, int n_ranges, const TrikHsvMaskOut& o);
+int launch_mask(const TrikHsvFrameBatch& b, const uint16_t* ranges, int n_ranges, int64_t ranges_stride,
+                const TrikHsvMaskOut& o, hipStream_t s);
 // preview_kernel then overlay_kernel (circle from sums[f * sums_pitch])
 int launch_preview(const PreviewArgs& a, const TrikHsvTargetSums* sums, int sums_pitch, hipStream_t s);
 // launch_preview's last kernel alone: overlay_kernel (the guide lines unless

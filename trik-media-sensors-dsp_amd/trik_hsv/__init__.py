@@ -17,7 +17,7 @@ import ctypes as C
 from typing import Iterable, Sequence, Tuple
 
 from . import _abi
-from ._abi import (CONVERT_HSV_PLANES, CONVERT_RGB888HSV, CONVERT_RGB_PLANES, FORMAT_RGB565X, FORMAT_UNKNOWN, FORMAT_YUV422, FORMAT_YUV422P,  # noqa: F401
+from ._abi import (MASK_BITS, MASK_BYTES, CONVERT_HSV_PLANES, CONVERT_RGB888HSV, CONVERT_RGB_PLANES, FORMAT_RGB565X, FORMAT_UNKNOWN, FORMAT_YUV422, FORMAT_YUV422P,  # noqa: F401
                    IALG_EFAIL, IALG_EOK, IVIDTRANSCODE_EFAIL, IVIDTRANSCODE_EOK,
                    IVIDTRANSCODE_EUNSUPPORTED, LAYOUT_OV7670, LAYOUT_YUYV, XDM_FLUSH,
                    XDM_GETBUFINFO, XDM_GETSTATUS, XDM_GETVERSION, XDM_RESET, XDM_SETDEFAULT,
@@ -641,6 +641,57 @@ def convert_batch(frames, width, height, line_length, layout, form=CONVERT_HSV_P
     rc = _lib.trik_hsv_convert_batch(C.byref(b), C.byref(o), _stream_ptr(stream, frames))
     if rc:
         raise TrikHsvError(rc, "trik_hsv_convert_batch")
+    return out
+
+
+def mask_batch(frames, width, height, line_length, layout, ranges, form=MASK_BITS, *, out=None, n_frames=None,
+               frame_stride=None, stream=None):
+    """The per-pixel detection mask of every frame (trik_hsv_mask_batch), bit for
+    bit the reference's detectHsvPixel: uint8 [N, T, H, W // 8] for MASK_BITS
+    (pixel c is bit c & 7 of byte c >> 3 of its row, least significant first)
+    or [N, T, H, W] for MASK_BYTES (0xFF detected, 0x00 not), plane t under
+    range t.  `ranges` is a CUDA tensor of int16 / uint16 read by the kernel in
+    stream order and never copied: [T, 6] is one set shared by every frame,
+    [N, T, 6] a set per frame (frame_ranges_batch's and ranges_of_detect's
+    buffer; its first stride may be larger than 6 T, the other axes
+    contiguous).  A host sequence [T][6] or [N][T][6] is uploaded on the
+    stream.  Returns a dense tensor it allocates, or fills `out` (a CUDA uint8
+    tensor of that shape whose last axis is contiguous; its other strides are
+    taken as they are, and the elements between its rows, planes and frames
+    are not written)."""
+    import torch
+
+    b = _batch(frames, width, height, line_length, layout, n_frames, frame_stride)
+    s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+    if not isinstance(ranges, torch.Tensor):
+        host = torch.tensor(ranges, dtype=torch.int32).to(torch.int16)  # (uint16 bits)
+        with torch.cuda.stream(s):
+            ranges = host.pin_memory().to(frames.device, non_blocking=True)
+    if (not ranges.is_cuda or ranges.dtype.itemsize != 2 or ranges.dtype.is_floating_point or ranges.dim() not in (2, 3)
+            or ranges.shape[-1] != 6 or ranges.shape[-2] < 1 or ranges.stride(-1) != 1 or ranges.stride(-2) != 6
+            or (ranges.dim() == 3 and ranges.shape[0] != b.n_frames)):
+        raise ValueError("ranges must be a CUDA (HIP) tensor [T, 6] or [n_frames, T, 6] of int16 or uint16 "
+                         "with contiguous tuples")
+    T = ranges.shape[-2]
+    ranges_stride = 0 if ranges.dim() == 2 else (ranges.stride(0) if b.n_frames > 1 else 6 * T)
+    row_bytes = width // 8 if form == MASK_BITS else width
+    shape = (b.n_frames, T, height, row_bytes)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != shape or (row_bytes > 1 and out.stride(-1) != 1):
+        raise ValueError(f"out must be a CUDA (HIP) uint8 tensor of shape {shape} with a contiguous last axis")
+    if out.numel() == 0:  # no frame or no pixel: the call writes nothing (and an empty tensor has no address)
+        return out
+    st = out.stride()
+    # (the stride of an axis of length 1 addresses nothing: the dense one stands for it)
+    row = st[2] if height > 1 else row_bytes
+    plane = st[1] if T > 1 else height * row
+    frame = st[0] if b.n_frames > 1 else (T - 1) * plane + height * row
+    o = _abi.MaskOut(out.data_ptr(), frame, plane, row, int(form))
+    rc = _lib.trik_hsv_mask_batch(C.byref(b), C.c_void_p(ranges.data_ptr()), T, ranges_stride, C.byref(o),
+                                  C.c_void_p(s.cuda_stream))
+    if rc:
+        raise TrikHsvError(rc, "trik_hsv_mask_batch")
     return out
 
 

@@ -38,6 +38,7 @@ LAYOUT_YUYV = 0
 LAYOUT_OV7670 = 1
 MAX_RANGES = 64
 CONVERT_RGB888HSV, CONVERT_HSV_PLANES, CONVERT_RGB_PLANES = 0, 1, 2  # TRIK_HSV_CONVERT_*
+MASK_BITS, MASK_BYTES = 0, 1  # TRIK_HSV_MASK_*
 BLOB_CHUNK_SLOTS = 4096  # TRIK_HSV_BLOB_CHUNK_SLOTS
 
 i32, i64, u8, u16, u64 = C.c_int32, C.c_int64, C.c_uint8, C.c_uint16, C.c_uint64
@@ -200,6 +201,11 @@ class ConvertOut(C.Structure):
                 ("form", i32)]
 
 
+class MaskOut(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("frame_stride", i64), ("plane_stride", i64), ("row_pitch", i32),
+                ("form", i32)]
+
+
 class TargetSums(C.Structure):
     _fields_ = [("points", i64), ("sum_x", i64), ("sum_y", i64)]
 
@@ -253,6 +259,7 @@ PROTOTYPES = {
                                      C.c_void_p], i32),
     "trik_hsv_ranges_of_detect": ([C.c_void_p, i32, C.c_void_p, i32, i32, C.c_void_p], i32),
     "trik_hsv_convert_batch": ([C.POINTER(FrameBatch), C.POINTER(ConvertOut), C.c_void_p], i32),
+    "trik_hsv_mask_batch": ([C.POINTER(FrameBatch), C.c_void_p, i32, i64, C.POINTER(MaskOut), C.c_void_p], i32),
     "trik_hsv_frame_ranges_preview": ([C.c_void_p, C.POINTER(FrameBatch), C.c_void_p, i32, i32, C.c_void_p, i32,
                                        i32, i32, i32, C.c_void_p, C.c_int64, C.c_void_p], i32),
     "trik_hsv_line_preview": ([C.c_void_p, C.POINTER(FrameBatch), i32, i32, C.c_void_p, i32, i32, i32,

@@ -3,11 +3,16 @@
 
   make -C trik-media-sensors-dsp_amd/csrc isa BUILD=/tmp/before   # at the parent
   make -C trik-media-sensors-dsp_amd/csrc isa BUILD=/tmp/after    # at the result
-  python scripts/isa_summary.py /tmp/before/isa /tmp/after/isa
+  python scripts/isa_summary.py /tmp/before/isa /tmp/after/isa [--pairs FILE]
+
+--pairs: a file of OLD=NEW lines, kernel names as the table prints them; a
+kernel NEW that the parent does not have is compared with the parent's OLD,
+whichever listing held it (a renamed kernel, a kernel moved to another file).
 
 For every kernel symbol: instruction count, VGPRs, SGPRs, static LDS bytes and
 scratch bytes before -> after, and how the instruction stream compares:
-  same   identical text
+  same   identical text (the function number of local labels, .LBB<n>_, aside:
+         it is the kernel's position in its file)
   regs   identical once register numbers are masked
   kernarg  identical once, besides, the immediate operands of scalar loads and
          scalar adds are masked: the kernel arguments moved (a member added to
@@ -23,6 +28,7 @@ import sys
 INFO = {"NumVgprs": "vgpr", "TotalNumSgprs": "sgpr", "ScratchSize": "scratch", "LDSByteSize": "lds"}
 REG = re.compile(r"\b([vsa])(\d+|\[\d+:\d+\])")
 IMM = re.compile(r"(?<![\w#])(0x[0-9a-f]+|-?\d+)\b")
+LABEL = re.compile(r"\.LBB\d+_")
 SCALAR = ("s_load_dword", "s_add_u32", "s_addc_u32", "s_add_i32", ".amdhsa_kernarg_size")
 
 
@@ -47,7 +53,7 @@ def kernels(path):
         if line.startswith(".Lfunc_end"):
             body = False
         elif body and line.startswith("\t") and not line.startswith("\t.") and not line.startswith("\t;"):
-            cur["ins"].append(line.split(";")[0].strip())
+            cur["ins"].append(LABEL.sub(".LBB_", line.split(";")[0].strip()))
         m = re.match(r"^; (\w+): (\d+)", line)
         if m and m.group(1) in INFO:
             cur[INFO[m.group(1)]] = int(m.group(2))
@@ -70,6 +76,12 @@ def short(name):
 
 def main():
     before, after = sys.argv[1], sys.argv[2]
+    pairs, old = {}, {}  # NEW -> OLD; the parent's kernels by printed name
+    if sys.argv[3:4] == ["--pairs"]:
+        pairs = dict(reversed(ln.strip().split("=")) for ln in open(sys.argv[4]) if "=" in ln)
+        for fb in glob.glob(os.path.join(before, "*.s")):
+            kb = kernels(fb)
+            old.update((short(n), kb[sym]) for sym, n in demangle(list(kb)).items())
     print("%-72s %-13s %-9s %-9s %-13s %-7s %s" % ("kernel", "instructions", "VGPR", "SGPR", "LDS", "scratch", "stream"))
     for fa in sorted(glob.glob(os.path.join(after, "*.s"))):
         fb = os.path.join(before, os.path.basename(fa))
@@ -77,7 +89,7 @@ def main():
         names = demangle(list(ka))
         print("# " + os.path.basename(fa).replace(".s", ".hip"))
         for sym, a in ka.items():
-            b = kb.get(sym)
+            b = kb.get(sym) or old.get(pairs.get(short(names[sym])))
             if b is None:
                 print("%-72s (not in the parent)" % short(names[sym]))
                 continue
@@ -92,8 +104,9 @@ def main():
             cols = ["%d->%d" % (b[k], a[k]) if b[k] != a[k] else "%d" % a[k] for k in ("vgpr", "sgpr", "lds", "scratch")]
             n = "%d->%d" % (len(b["ins"]), len(a["ins"])) if len(b["ins"]) != len(a["ins"]) else "%d" % len(a["ins"])
             print("%-72s %-13s %-9s %-9s %-13s %-7s %s" % (short(names[sym])[:72], n, *cols, stream))
-        for sym in kb:
-            if sym not in ka:
+        gone = demangle([sym for sym in kb if sym not in ka])
+        for sym in gone:
+            if short(gone[sym]) not in pairs.values():
                 print("%-72s (gone)" % sym)
 
 

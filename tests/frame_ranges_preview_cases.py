@@ -7,7 +7,8 @@ trik_hsv_frame_ranges_preview on the GPU).
 plan() restates launch_frame_ranges_preview
 (trik-media-sensors-dsp_amd/csrc/trik_hsv_frame_ranges_preview.hip): the 2:1
 kernel under preview_cases.forms()'s conditions (the predicate it shares with
-launch_rows2), the gather otherwise.  In both a wave takes tasks of 64 lanes
+launch_rows2), the gather otherwise (the line sensors' launcher in the same
+file: line_frame_ranges_preview_cases.forms()).  In both a wave takes tasks of 64 lanes
 of ONE frame -- 64 units of 8 output pixels, or 128 four-byte output groups --
 round robin over the grid's waves; a frame is ceil(per_frame / per task) tasks,
 the last of them with idle lanes.

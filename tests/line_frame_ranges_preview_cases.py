@@ -7,7 +7,7 @@ trik_hsv_line_frame_ranges_preview on the GPU).
 
 forms() restates line_frame_ranges_preview_core and
 launch_line_frame_ranges_preview
-(trik-media-sensors-dsp_amd/csrc/trik_hsv_line_frame_ranges_preview.hip):
+(trik-media-sensors-dsp_amd/csrc/trik_hsv_frame_ranges_preview.hip):
 ensure_maps with the layout's column window (ov7670: source columns 5..W-5),
 then the 2:1 kernel where the windowed maps are the 2:1 ones, the overlay maps
 are monotone (ovl_ok) and preview_rows2_ok's conditions hold -- its WIN form

@@ -1,6 +1,7 @@
-"""trik_hsv_frame_ranges_preview (fr_preview_rows2_kernel, fr_preview_gather_kernel
-of trik-media-sensors-dsp_amd/csrc/trik_hsv_frame_ranges_preview.hip, then
-overlay_kernel) on the GPU, byte for byte:
+"""trik_hsv_frame_ranges_preview (fr_preview_rows2_kernel and
+fr_preview_gather_kernel of
+trik-media-sensors-dsp_amd/csrc/trik_hsv_frame_ranges_preview.hip under its
+HsvTest, then overlay_kernel) on the GPU, byte for byte:
 
 a. the range follows the frame: small frames, one task each, a range per frame;
 b. grid passes: every wave takes three tasks and some a fourth, of other frames

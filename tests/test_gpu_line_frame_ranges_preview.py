@@ -1,7 +1,8 @@
-"""trik_hsv_line_frame_ranges_preview (lfr_preview_rows2_kernel,
-lfr_preview_gather_kernel of
-trik-media-sensors-dsp_amd/csrc/trik_hsv_line_frame_ranges_preview.hip, then
-line_overlay_kernel behind the gather) on the GPU, byte for byte, both layouts:
+"""trik_hsv_line_frame_ranges_preview (fr_preview_rows2_kernel and
+fr_preview_gather_kernel of
+trik-media-sensors-dsp_amd/csrc/trik_hsv_frame_ranges_preview.hip under its
+ValTest, then line_overlay_kernel behind the gather) on the GPU, byte for byte,
+both layouts:
 
 a. the range follows the frame: small frames, one task each, a V range per
    frame, an empty one and one above 100 among them;

@@ -485,8 +485,8 @@ int launch_preview_rows2(const PreviewArgs& a, hipStream_t s);
 // sensor's band lines), fused into one pass where the 2:1 kernel applies
 int launch_line_preview(PreviewArgs a, const TrikHsvTargetSums* sums, int band, hipStream_t s);
 // The line sensors' previews with a V range PER FRAME, read on the device
-// (trik_hsv_line_frame_ranges_preview.hip; no table, a.tables and a.range are
-// not read): frame f under entries 4 and 5 of ranges + 6 f in percent, the
+// (trik_hsv_frame_ranges_preview.hip, the same two kernel templates under the
+// V test; no table, a.tables and a.range are not read): frame f under entries 4 and 5 of ranges + 6 f in percent, the
 // overlays with sums[f]; a.layout picks the sensor (ov7670: band lines, and the
 // caller's maps carry its column window; YUYV: the webcam line sensor).
 int launch_line_frame_ranges_preview(const PreviewArgs& a, const uint16_t* ranges, const TrikHsvTargetSums* sums,

@@ -25,6 +25,7 @@
 
 #include "trik_hsv_internal.h"
 #include "trik_hsv_pixel.h"
+#include "trik_hsv_preview_px.h"
 #include "trik_hsv_stripe_px.h"
 #include "trik_hsv_wave.h"
 
@@ -71,7 +72,6 @@ void preview_gather_kernel(PreviewArgs a, PreviewGeom g) {
   const uint32_t hue_lane = (uint32_t)offsetof(StripeTables, hue) + ((t % kHueCopies) << 2);
   const uint32_t m43_lane = (uint32_t)offsetof(StripeTables, m43) + ((t % kM43Copies) << 2);
   const uint32_t qpr = g.per_row.d;
-  const int64_t ll = a.line_length;
   // kQ output groups per thread, 64 apart (each load and store instruction of
   // a wave stays on consecutive groups), in phases (positions, map loads, frame
   // loads, arithmetic, stores) so that a thread's loads are in flight together:
@@ -109,19 +109,7 @@ void preview_gather_kernel(PreviewArgs a, PreviewGeom g) {
       for (int k = 0; k < 2; ++k) {
         w[u][k] = 0u;
         if (sr[u] < 0 || sc[u][k] < 0) continue;
-        if (a.layout == TRIK_HSV_LAYOUT_YUYV && a.aligned4) {
-          w[u][k] = *reinterpret_cast<const uint32_t*>(fr + (int64_t)sr[u] * ll + 4 * (sc[u][k] >> 1));
-        } else if (a.layout == TRIK_HSV_LAYOUT_OV7670 && a.aligned4) {
-          // Y from the luma plane, the V, U byte pair as one u16 (OSEQ:343-387)
-          const int64_t off = (int64_t)sr[u] * ll + sc[u][k];
-          const uint32_t Y = fr[off];
-          const uint32_t vu = *reinterpret_cast<const uint16_t*>(fr + ll * a.height + (off & ~(int64_t)1));
-          w[u][k] = Y | ((vu >> 8) << 8) | ((vu & 0xFFu) << 24);
-        } else {
-          int Y, U, V;
-          fetch_yuv(fr, a.height, a.line_length, a.layout, sr[u], sc[u][k], Y, U, V);
-          w[u][k] = (uint32_t)Y | ((uint32_t)U << 8) | ((uint32_t)V << 24);
-        }
+        w[u][k] = preview_px::gather_word(fr, a, a.layout, a.aligned4, sr[u], sc[u][k]);
       }
     }
     uint32_t out[kQ];
@@ -131,9 +119,7 @@ void preview_gather_kernel(PreviewArgs a, PreviewGeom g) {
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         if (sr[u] < 0 || sc[u][k] < 0) continue;
-        uint32_t x = w[u][k];
-        if (a.layout == TRIK_HSV_LAYOUT_YUYV && a.aligned4 && (sc[u][k] & 1))
-          x = __builtin_amdgcn_perm(x, x, 0x03020102u);
+        const uint32_t x = preview_px::y_first(w[u][k], a.layout, a.aligned4, sc[u][k]);
         const Phase1 p = phase1<0>(x, x ^ 0xFF00FF00u, m43_lane);
         uint32_t det;
         if (a.meta) {
@@ -151,12 +137,7 @@ void preview_gather_kernel(PreviewArgs a, PreviewGeom g) {
     for (int u = 0; u < kQ; ++u) {
       if (!ok[u]) continue;
       uint8_t* row = a.previews + (int64_t)ff[u] * a.preview_stride + (int64_t)rr[u] * a.out_ll;
-      const int b0 = 4 * (int)qq[u];
-      if (a.aligned4 && b0 + 4 <= a.out_ll) {
-        __builtin_nontemporal_store(out[u], reinterpret_cast<uint32_t*>(row + b0));  // (as the 2:1 kernel's)
-      } else {
-        for (int k = 0; k < 4 && b0 + k < a.out_ll; ++k) row[b0 + k] = (uint8_t)(out[u] >> (8 * k));
-      }
+      preview_px::store_group(row, 4 * (int)qq[u], a.out_ll, a.aligned4, out[u]);
     }
   }
 }
@@ -260,7 +241,7 @@ void preview_rows2_kernel(PreviewArgs a, PreviewRowsGeom g) {
     }
 #pragma unroll
     for (int u = 0; u < kRowsQ; ++u) {
-      uint32_t ws[PX];
+      uint32_t ws[PX];  // (preview_px::unit_words' text: calling it moves this kernel's schedule)
       if (YUYV) {
         ws[0] = w[u].x; ws[1] = w[u].y; ws[2] = w[u].z; ws[3] = w[u].w;
         ws[4] = wc[u].x; ws[5] = wc[u].y; ws[6] = wc[u].z; ws[7] = wc[u].w;
@@ -277,15 +258,7 @@ void preview_rows2_kernel(PreviewArgs a, PreviewRowsGeom g) {
       uint32_t t_lo = 1u, t_hi = 0u;
       bool band_row = false;
       if (OVL) {
-        const uint32_t n = tpts[u];
-        if (n > 10) {  // LSEQ:464-474: drawRgbTargetCenterLine(targetX), columns cx - 1 .. cx + 1
-          const int32_t cx = (int32_t)(tsx[u] / n), wm = a.width - 1;
-          const int32_t c0 = cx - 1 < 0 ? 0 : (cx - 1 > wm ? wm : cx - 1);
-          const int32_t c1 = cx + 1 < 0 ? 0 : (cx + 1 > wm ? wm : cx + 1);
-          // ovl_half: wi2wo[c] = c / 2 (the 2:1 maps), no dependent map loads
-          t_lo = a.ovl_half ? (uint32_t)c0 >> 1 : a.wi2wo[c0];
-          t_hi = a.ovl_half ? (uint32_t)c1 >> 1 : a.wi2wo[c1];
-        }
+        preview_px::target_columns(a, tpts[u], tsx[u], t_lo, t_hi);
         band_row = (int32_t)rr[u] == a.ovl_band[0] || (int32_t)rr[u] == a.ovl_band[1];
       }
       uint32_t v[PX];
@@ -311,6 +284,7 @@ void preview_rows2_kernel(PreviewArgs a, PreviewRowsGeom g) {
         const uint32_t c565 = bfi32(0xF800u, (uint32_t)p.b << 8, bfi32(0x07E0u, (uint32_t)p.g << 3, (uint32_t)p.r >> 3));
         v[k] = det ? 0xFFE0u : c565;
         if (WIN) v[k] = c >= (uint32_t)a.rows2_c0 && c < (uint32_t)a.rows2_c1 ? v[k] : 0u;
+        // (preview_px::line_overlay_px's text, kept here for the same reason)
         if (OVL) {  // thin lines (magenta) first, then the band and target lines (red) over them
           const bool mag = (int32_t)c == a.ovl_mag[0] || (int32_t)c == a.ovl_mag[1] ||
                            (int32_t)c == a.ovl_mag[2] || (int32_t)c == a.ovl_mag[3];
@@ -326,10 +300,8 @@ void preview_rows2_kernel(PreviewArgs a, PreviewRowsGeom g) {
       if (ff[u] < nf) {
         uint8_t* dst = a.previews + (uint64_t)ff[u] * (uint32_t)a.preview_stride +
                        (__umul24(rr[u], (uint32_t)a.out_ll) + 2u * PX * qq[u]);
-        // nontemporal stores: the preview is written once and not read back
-        // here (630 MB per 4096 VGA frames; plain stores left back-to-back
-        // batches waiting on the write-backs: 0.51 -> 0.45-0.47 ms,
-        // scripts/ab/r05zc_preview_nt.py)
+        // (preview_px::store_unit's text, kept here for the same reason; why
+        // nontemporal is said there)
 #pragma unroll
         for (int h = 0; h < PX / 4; ++h) {
           u32x2 o;
@@ -767,9 +739,9 @@ __global__ __launch_bounds__(kRangeBlock) void auto_range_vec_kernel(AutoRangeAr
 }  // namespace
 
 // Whether the 2:1 row kernels take this call's maps, layout, alignment and
-// sizes: preview_rows2_kernel here and the per-frame-range twin
+// sizes: preview_rows2_kernel here and fr_preview_rows2_kernel
 // (trik_hsv_frame_ranges_preview.hip) read and write the same units under the
-// same 32-bit offsets, so both launchers ask this one predicate.
+// same 32-bit offsets, so all three launchers ask this one predicate.
 bool preview_rows2_ok(const PreviewArgs& a) {
   const bool yuyv = a.layout == TRIK_HSV_LAYOUT_YUYV;
   const int px = 8;  // output pixels per unit

@@ -138,7 +138,10 @@ def test_mxn_every_yuv_triple(hsv, det, table):
     a frame holds 48 pairs in rows 0..2 (row 3 belongs to no cell)."""
     import torch
 
+    # 174,763 frames x 96 cells is just over the blocks one launch holds (2^32 / 256 threads): launch_mxn
+    # splits this batch in two, the suite's only run of its frame loop.  Keep that when resizing.
     nf = -(-(1 << 23) // 48)
+    assert nf * 96 > 0xFFFFFFFF // 256
     p = np.arange(nf * 48, dtype=np.int64) % (1 << 23)
     u, v, k = p & 255, (p >> 8) & 255, p >> 16
     y = np.stack([2 * k, 2 * k + 1], -1).reshape(nf, 3, 32)

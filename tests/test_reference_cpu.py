@@ -16,6 +16,7 @@ import pytest
 import blob_patterns
 import jpeg_cases
 import jpeg_ref
+import mxn_cases
 import mxn_ref
 import preview_cases
 import ref_lib
@@ -505,6 +506,45 @@ def test_mxn_tie_frames(table):
         assert rc == 0 and got == [color_of[b] for b in want]
         cnt += len(want)
     assert cnt == 5
+
+
+def test_mxn_shape_frames(table):
+    """The frames of tests/mxn_cases.py, the inputs tests/test_gpu_mxn_shapes.py
+    judges the GPU by: every edge, split and whole-frame cell in the
+    reference's own loop, and the preview geometries (gaps, overlaps, clamped
+    squares, outputs larger than the input) in its own preview pass.  The
+    reference gives colours only; the contenders of a cell differ in colour
+    from each other and from every other bin of the frame, so the colour of
+    the cell names its winner."""
+    pal = mxn_cases.Palette(table)
+    color_of = {b: mxn_ref.bin_color(b) for b in range(mxn_ref.N_BINS)}
+    cnt = 0
+    edges = mxn_cases.edge_cases(pal)
+    splits, bigs = mxn_cases.split_cases(pal), mxn_cases.big_cases(pal)
+    for c in edges + splits + bigs:
+        w, h, m, n = c.geom
+        k = c.cell[0] * n + c.cell[1]
+        if isinstance(c, mxn_cases.EdgeCase):
+            win, lose = (c.X, [c.Y, pal.C]) if c.kind == "lead" else (c.Y, [c.X, pal.C])
+        elif isinstance(c, mxn_cases.SplitCase):
+            win = mxn_ref.winner_sequential(c.bins.reshape(-1).tolist())
+            lose = [b for b in set(c.bins.reshape(-1).tolist()) if b != win]
+        else:
+            win = pal.A if c.name == "big_tie" else pal.C
+            lose = [b for b in (pal.A, pal.B, pal.C, pal.noise[0]) if b != win]
+        assert all(color_of[b] != color_of[win] for b in lose), c
+        bins, _ = _same_mxn(table, pal.frame(c.bins), w, h, w, m, n, w // 2, h // 2, w, c.name)
+        assert bins[k] == win, c
+        rc, got, _ = ref_lib.mxn_run(pal.frame(c.bins), w, h, w, m, n)
+        assert rc == 0 and got[k] == color_of[win], (c, got[k])
+        cnt += 1
+    for w, h, ll, m, n, ow, oh, oll in mxn_cases.PREVIEW_GEOMS:
+        for i in range(mxn_cases.PREVIEW_FRAMES):
+            fr = pal.frame(mxn_cases.preview_body(pal, w, h, i), ll)
+            _same_mxn(table, fr, w, h, ll, m, n, ow, oh, oll, (w, h, ll, m, n, ow, oh, oll))
+            cnt += 1
+    assert cnt == len(edges) + len(splits) + len(bigs) + 4 * 2
+    assert len(edges) >= 250 and len(splits) == 10 and len(bigs) == 2
 
 
 def test_mxn_gpu_test_geometries(oracle_mod, table):
